@@ -1,7 +1,7 @@
 """Training-throughput bench of the SimpleAICV DDP hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model resnet50|vit_base_patch16|sam_b_encoder|resnet50_detr|resnet50_detr_config|resnet50_retinanet|resnet50_fcos|sam_b]
-                    [--batch B] [--no-cpu-baseline] [--no-secondary] [--eager]
+                    [--batch B] [--eager] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-secondary] ...]
 
 A step = forward + loss + backward + gradient all-reduce + optimizer step of one per-GPU batch of synthetic data that
 is resident in HBM before timing starts.  `--gpus N` with N > 1 starts N ranks itself (one process per GPU, RCCL via
@@ -13,9 +13,15 @@ reference train_config.py (00.classification_training/imagenet/<model>/train_con
 -> build_training_mode -> tools.scripts.train_classification over a loader of K device-resident batches.  With one GPU
 the loop runs each iteration as a replayed hipGraph (config.use_step_graph, engine.StepGraph); `--eager` turns that off.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  `value` / `ms_per_step` are the MEDIAN of several
-timed windows of exactly K steps each (each bracketed by barrier + synchronize; max over ranks), enough windows for
->= 5 s of timed GPU work; all windows are listed.  Extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up and times ONE window of
+exactly K steps (bracketed by barrier + synchronize; max over ranks): `value` / `ms_per_step` come from it.
+`--dump-outputs DIR` then writes what the timed path handed its caller after its last step (dump_outputs).  The step runs in
+the deterministic mode tools.utils.set_seed() selects, so those outputs are the same on every run; `--atomics` times the
+fast fp32-atomics form instead.
+`--full` adds everything else, as the default line carried it before: `value` / `ms_per_step` become the MEDIAN of
+several timed windows of exactly K steps each, enough windows for >= 5 s of timed GPU work (all windows are listed),
+and the line gets the extra objects:
+  power        -- socket power and shader clock sampled while the same steps replay after the timed windows;
   roofline     -- the dominant kernel (implicit-GEMM conv, MFMA-bound) priced from HIP events around every one of its
                   launches in an eager pass of the same steps right after the timed windows (events cannot bracket
                   kernels inside a replayed graph);
@@ -80,12 +86,20 @@ def parse():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--model', default='resnet50')
     ap.add_argument('--batch', type=int, default=None, help='per-GPU batch (default 256; 8 for sam_b_encoder / resnet50_detr)')
-    ap.add_argument('--min-gpu-seconds', type=float, default=5.0, help='timed windows are repeated until this much timed work ran')
-    ap.add_argument('--max-windows', type=int, default=15)
+    ap.add_argument('--full', action='store_true',
+                    help='also the repeated timed windows, power sample, kernel pricing pass, secondary workloads and CPU baseline '
+                         '(a plain run times one window of --steps steps and prints the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the loss and the trained parameters / buffers as DIR/<name>.npy')
+    ap.add_argument('--min-gpu-seconds', type=float, default=5.0, help='--full: timed windows are repeated until this much timed work ran')
+    ap.add_argument('--max-windows', type=int, default=15, help='--full: at most this many timed windows')
     ap.add_argument('--eager', action='store_true', help='no step graph (one kernel launch per kernel from Python)')
     ap.add_argument('--graph', action='store_true', help='force the step graph also with several ranks')
     ap.add_argument('--deterministic', action='store_true',
-                    help='fixed-order BatchNorm statistics, as the entry scripts run after set_seed() (default: fp32 atomics)')
+                    help='(the default: every reduction ordered, as the entry scripts run after set_seed(); kept for old command lines)')
+    ap.add_argument('--atomics', action='store_true',
+                    help='time the fast form instead: reductions and BatchNorm statistics added with fp32 atomics in completion order '
+                         '(results differ from run to run)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-secondary', action='store_true')
     ap.add_argument('--no-kernel-timer', action='store_true')
@@ -335,6 +349,34 @@ def _replay_host_ms(state):
     return round(g.replay_host_s / g.replays * 1e3, 3)
 
 
+DUMP_BYTES = 56 * 2 ** 20       # data budget of --dump-outputs (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(out_dir, model, state):
+    """--dump-outputs DIR: what the timed path handed its caller after its last step, as DIR/<name>.npy --
+    `loss` (float64: the loss the loop returned for the timed window; the step workloads' last-step loss), and every
+    parameter (`param.<name>`) and buffer (`buffer.<name>`) of the trained model (floating tensors as float32 -- float64
+    stays float64 --, integer ones as float64).  Inputs, weights and step count depend on the arguments only, so two builds
+    run with the same arguments can be compared file for file.  A tensor larger than its share of DUMP_BYTES is written as a
+    fixed sample: the elements at sorted flat indices drawn from a generator seeded by the tensor's name."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'loss.npy'), np.asarray(float(state['loss']), dtype=np.float64))
+    net = getattr(model, 'module', model)
+    tensors = [('param.' + n, p) for n, p in net.named_parameters()] + [('buffer.' + n, b) for n, b in net.named_buffers()]
+    share = max(1, DUMP_BYTES // 8 // max(1, len(tensors)))        # elements per tensor, at float64's 8 bytes
+    for name, t in tensors:
+        flat = t.detach().reshape(-1)
+        if flat.numel() > share:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.sort(rng.choice(flat.numel(), size=share, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        dtype = flat.dtype if flat.dtype in (torch.float32, torch.float64) else (torch.float32 if flat.is_floating_point() else torch.float64)
+        np.save(os.path.join(out_dir, name + '.npy'), flat.to(dtype).cpu().numpy())
+
+
 def measure(name, args, world, rank, device, use_graph, primary):
     """-> result dict of one workload (timed windows, kernel pricing pass)."""
     import torch
@@ -373,8 +415,10 @@ def measure(name, args, world, rank, device, use_graph, primary):
             dt = float(t)
         windows.append(dt)
         host.append(th)
-        if len(windows) >= budget_windows or sum(windows) >= (args.min_gpu_seconds if primary else args.min_gpu_seconds / 2):
+        if not args.full or len(windows) >= budget_windows or sum(windows) >= (args.min_gpu_seconds if primary else args.min_gpu_seconds / 2):
             break
+    if primary and args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, state)
     med = statistics.median(windows)
     ms = med / args.steps * 1e3
     value = batch * world * args.steps / med
@@ -387,6 +431,7 @@ def measure(name, args, world, rank, device, use_graph, primary):
                    'final_loss': round(float(state['loss']), 4), 'loss_scale': scaler.get_scale() if scaler is not None else None,
                    'step_graph': bool(use_graph), 'step_graphs': state.get('step_graphs') if isinstance(state, dict) else None,
                    'bn_statistics': 'fp32 atomics into pooled rows (SAICV_BN_INLINE=1)' if ops.BN_INLINE else 'fixed-order partial rows',
+                   'deterministic': ops.is_deterministic(),
                    'host_ms_per_step': round(statistics.median(host) / args.steps * 1e3, 3),
                    # host time spent ISSUING a step when it is a graph replay (input copies, hyper-parameter refresh,
                    # hipGraphLaunch); host_ms_per_step above also contains the loop's lagged read of the loss, i.e. waiting
@@ -404,10 +449,10 @@ def measure(name, args, world, rank, device, use_graph, primary):
     # ---- socket power and shader clock while the same steps replay (rocm-smi polled from a thread for ~1.5 s, AFTER the timed windows).
     # r05 finding: the GEMM kernels of these steps run AT the 1 400 W socket limit on random operands and the shader clock gives way
     # (2.0-2.2 of 2.4 GHz): `power` says how close the whole step sits to that limit.
-    if world == 1 and not getattr(args, 'no_power', False):
+    if args.full and world == 1 and not getattr(args, 'no_power', False):
         res['power'] = sample_power(lambda: run(args.steps), fence)
     # ---- price the dominant kernel: an eager pass of the same steps with HIP events on the launch stream
-    if not args.no_kernel_timer:
+    if args.full and not args.no_kernel_timer:
         cfg_graph = name in CONFIG_DIR and use_graph
         ops.KernelTimer.only = {'igemm_nt'} if args.dominant_only else None
         ops.KernelTimer.records = []
@@ -740,12 +785,16 @@ def cpu_reference_child(threads):
 
 # ------------------------------------------------------------------------------------------ worker
 def worker(args):
-    # BatchNorm statistics: the entry scripts' set_seed() selects the fixed-order (bit-reproducible) sums, as the reference's
-    # set_seed asks for deterministic kernels; the benchmark opts into the atomically accumulated ones (0.35-0.4 ms per
-    # ResNet-50 step) unless --deterministic, and says so in its JSON line (config.bn_statistics)
-    if not args.deterministic:
+    # The timed step is the deterministic mode the entry scripts' set_seed() selects, as the reference's set_seed asks for
+    # deterministic kernels: every reduction of the library ordered, BatchNorm statistics as fixed-order partial rows.  With the same
+    # arguments a run then computes the same result every time (--dump-outputs compares bit for bit); the hand-written step workloads,
+    # which do not call set_seed(), get it at import.  --atomics times the fast form (fp32 atomics in completion order, about 0.3 ms
+    # less per ResNet-50 step, results that differ from run to run); the JSON line says which ran (config.bn_statistics / deterministic)
+    if args.atomics:
         os.environ.setdefault('SAICV_BN_INLINE', '1')
         os.environ.setdefault('SAICV_DETERMINISTIC', '0')
+    else:
+        os.environ.setdefault('SAICV_DETERMINISTIC', '1')
     import torch
     import torch.distributed as dist
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -798,7 +847,7 @@ def worker(args):
     if watchdog is not None:
         watchdog.finished()             # this rank's captured step replayed and was timed; rank 0 decides for everybody
     secondary = None
-    if args.model == 'resnet50' and not args.no_secondary:
+    if args.full and args.model == 'resnet50' and not args.no_secondary:
         import gc
         gc.collect()
         torch.cuda.empty_cache()
@@ -808,7 +857,7 @@ def worker(args):
         if guard:
             watchdog.finished()
     sam = None
-    if args.model == 'resnet50' and not args.no_secondary and not args.no_sam and world == 1:
+    if args.full and args.model == 'resnet50' and not args.no_secondary and not args.no_sam and world == 1:
         # BASELINE.json configs[4] on the driver line: SAM ViT-B image encoder, 3 x 1024 x 1024, the reference's per-GPU batch of
         # 20 (sam_b_training/train_config.py:221), ONE timed window of 5 steps (~0.6 s) + the kernel pricing pass
         import argparse as _ap
@@ -828,7 +877,7 @@ def worker(args):
         except Exception as e:      # noqa: BLE001 -- the headline must not die with the third object
             sam = {'error': f'{type(e).__name__}: {e}'}
     detr = None
-    if args.model == 'resnet50' and not args.no_secondary and not args.no_sam and world == 1:
+    if args.full and args.model == 'resnet50' and not args.no_secondary and not args.no_sam and world == 1:
         # BASELINE.json configs[3] on the driver line (r05): the reference's DETR-R50 config through tools.scripts.train_detection,
         # per-GPU batch 8, the whole step captured (Hungarian assignment on the device); ONE window of 5 steps
         import argparse as _ap
@@ -849,7 +898,7 @@ def worker(args):
             detr = {'error': f'{type(e).__name__}: {e}'}
 
     sam_full = None
-    if args.model == 'resnet50' and not args.no_secondary and not args.no_sam and world == 1:
+    if args.full and args.model == 'resnet50' and not args.no_secondary and not args.no_sam and world == 1:
         # BASELINE.json configs[4] as the reference trains it (r06): the FULL SAM step -- image encoder + 1 + decoder_iters prompt /
         # decoder passes + SAMLoss + AdamW -- through tools.interactive_segmentation_scripts.train_sam_segmentation and the reference's
         # config, per-GPU batch 8 (eager launches unless SAICV_SAM_GRAPH=1: then one graph per drawn prompt combination, the 12 warm-up
@@ -879,8 +928,9 @@ def worker(args):
         if reexeced:
             out['graph_fallback'] = ('the captured N-rank step did not finish within the watchdog limit on every rank; the job '
                                      're-executed itself with --eager (collective decision over the process-group store)')
-        out['timing'] = (f'median of {len(primary["windows_ms_per_step"])} windows of exactly {args.steps} steps, each bracketed by '
-                         'barrier + synchronize (max over ranks)')
+        out['timing'] = ((f'median of {len(primary["windows_ms_per_step"])} windows of exactly {args.steps} steps, each bracketed by '
+                          'barrier + synchronize (max over ranks)') if args.full else
+                         f'one window of exactly {args.steps} steps, bracketed by barrier + synchronize (max over ranks)')
         if secondary is not None:
             out['secondary'] = {'metric': 'training images/sec/node', 'unit': 'images/s', **secondary}
         if sam is not None:
@@ -889,7 +939,7 @@ def worker(args):
             out['resnet50_detr_config'] = {'metric': 'training images/sec/node', 'unit': 'images/s', **detr}
         if sam_full is not None:
             out['sam_b'] = {'metric': 'training images/sec/node', 'unit': 'images/s', **sam_full}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args.model)
         line = json.dumps(out)
     if world > 1:

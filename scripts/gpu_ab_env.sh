@@ -8,7 +8,7 @@ i=0
 for v in "$@"; do
   i=$((i+1))
   for rep in 1 2; do
-    env $v timeout 600 python bench.py --model $MODEL --no-secondary --no-cpu-baseline --max-windows 2 > $O/${MODEL}_${i}_$rep.log 2>&1
+    env $v timeout 600 python bench.py --full --model $MODEL --no-secondary --no-cpu-baseline --max-windows 2 > $O/${MODEL}_${i}_$rep.log 2>&1
     echo "variant $i ($v) rep $rep: $(tail -1 $O/${MODEL}_${i}_$rep.log | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["value"])' 2>&1 | tail -1)"
   done
 done

@@ -14,5 +14,5 @@ for l in open('$O/lbench_$i.jsonl'):
     except Exception: continue
     print(d['M'], d['K'], d['N'], 'fwd_tf', d['fwd_tf'], 'dgrad_tf', d['dgrad_tf'], 'wgrad_tf', d['wgrad_tf'])
 PY
-  env $v timeout 600 python bench.py --model $MODEL --no-secondary --no-cpu-baseline --max-windows 2 > $O/${MODEL}_$i.log 2>&1; tail -1 $O/${MODEL}_$i.log | cut -c1-160
+  env $v timeout 600 python bench.py --full --model $MODEL --no-secondary --no-cpu-baseline --max-windows 2 > $O/${MODEL}_$i.log 2>&1; tail -1 $O/${MODEL}_$i.log | cut -c1-160
 done

@@ -8,7 +8,7 @@ LF_ENVS="X=0;SAICV_NT_STAGGER2=2;SAICV_NT_STAGGER2=4;SAICV_NT_STAGGER2=8;SAICV_N
 DG_ENVS="X=0;SAICV_NT_STAGGER2=2;SAICV_NT_STAGGER2=4;SAICV_NT_STAGGER2=2,SAICV_NT_STAGGER2_PCT=150" timeout 600 python scripts/dgrad_fused_bench.py > $O/dgrad_fused.jsonl 2> $O/dgrad_fused.err; grep model_weighted $O/dgrad_fused.jsonl; tail -2 $O/dgrad_fused.err
 for v in "X=0" "SAICV_NT_STAGGER2=2" "SAICV_NT_STAGGER2=4"; do
   for m in resnet50 vit_base_patch16; do
-    env $v timeout 600 python bench.py --model $m --no-secondary --no-cpu-baseline --max-windows 3 > $O/bench_${m}_$(echo $v | tr -c 'a-zA-Z0-9\n' '_').log 2>&1
+    env $v timeout 600 python bench.py --full --model $m --no-secondary --no-cpu-baseline --max-windows 3 > $O/bench_${m}_$(echo $v | tr -c 'a-zA-Z0-9\n' '_').log 2>&1
     echo "$v $m: $(tail -1 $O/bench_${m}_$(echo $v | tr -c 'a-zA-Z0-9\n' '_').log | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["value"])' 2>&1 | tail -1)"
   done
 done

@@ -6,8 +6,8 @@ timeout 600 python -m pytest tests/test_gpu_ddp.py -m gpu -q -x -k "captured" > 
 timeout 900 python -m pytest tests/test_gpu_sam.py -m gpu -q -x > $O/pytest_sam.log 2>&1; tail -2 $O/pytest_sam.log | cut -c1-300
 for m in resnet50_retinanet; do
   for e in "" "--eager"; do
-    timeout 600 python bench.py --model $m $e --no-secondary --no-cpu-baseline --max-windows 3 > $O/bench_${m}_${e#--}.log 2>&1
+    timeout 600 python bench.py --full --model $m $e --no-secondary --no-cpu-baseline --max-windows 3 > $O/bench_${m}_${e#--}.log 2>&1
     echo "$m $e: $(tail -1 $O/bench_${m}_${e#--}.log | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["value"], d["config"]["step_graph"], d["config"].get("host_enqueue_ms_per_step"))' 2>&1 | tail -1)"
   done
 done
-timeout 600 python bench.py --model sam_b_encoder --batch 20 --steps 5 --warmup 2 --max-windows 2 --no-secondary --no-cpu-baseline > $O/bench_sam_enc.log 2>&1; tail -1 $O/bench_sam_enc.log | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print("sam_b_encoder", d["ms_per_step"], d["value"], d.get("kernel_breakdown_ms_per_step"))'
+timeout 600 python bench.py --full --model sam_b_encoder --batch 20 --steps 5 --warmup 2 --max-windows 2 --no-secondary --no-cpu-baseline > $O/bench_sam_enc.log 2>&1; tail -1 $O/bench_sam_enc.log | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print("sam_b_encoder", d["ms_per_step"], d["value"], d.get("kernel_breakdown_ms_per_step"))'

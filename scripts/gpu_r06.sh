@@ -51,7 +51,7 @@ for step in "$@"; do
         i=0
         for v in "${V[@]}"; do
           i=$((i+1)); e=$(echo "$v" | tr '+' ' '); [ "$v" == "-" ] && e=""
-          env $e timeout 600 python bench.py --model $model --no-secondary --no-cpu-baseline --no-sam --max-windows ${ABWIN:-2} > $O/ab_${model}_${i}_$rep.log 2>&1
+          env $e timeout 600 python bench.py --full --model $model --no-secondary --no-cpu-baseline --no-sam --max-windows ${ABWIN:-2} > $O/ab_${model}_${i}_$rep.log 2>&1
           echo "ab $model variant $i [$e] rep $rep: $(benchval $O/ab_${model}_${i}_$rep.log)"
         done
       done ;;
@@ -61,7 +61,7 @@ for step in "$@"; do
       for rep in $(seq 1 $REPS); do
         for v in "${V[@]}"; do
           n=$(echo "$v" | tr -c 'a-zA-Z0-9\n' '_')
-          timeout 600 python scripts/with_lib.py "$v" bench.py --model $model --no-secondary --no-cpu-baseline --no-sam --max-windows ${ABWIN:-2} > $O/abl_${model}_${n}_$rep.log 2>&1
+          timeout 600 python scripts/with_lib.py "$v" bench.py --full --model $model --no-secondary --no-cpu-baseline --no-sam --max-windows ${ABWIN:-2} > $O/abl_${model}_${n}_$rep.log 2>&1
           echo "abl $model lib [$v] rep $rep: $(benchval $O/abl_${model}_${n}_$rep.log)"
         done
       done ;;
@@ -99,7 +99,7 @@ for step in "$@"; do
       done
       python scripts/pmc_fold.py $O/${name}_${model}_1 $O/${name}_${model}_2 > $O/${name}_${model}.json 2> $O/${name}_${model}.err; head -c 600 $O/${name}_${model}.json; tail -2 $O/${name}_${model}.err; rm -rf $O/${name}_${model}_1 $O/${name}_${model}_2 ;;
     bench)  timeout 900 python bench.py ${arg:-} > $O/bench_$(echo "${arg:-default}" | tr -c 'a-zA-Z0-9\n' '_').log 2>&1; tail -1 $O/bench_$(echo "${arg:-default}" | tr -c 'a-zA-Z0-9\n' '_').log | cut -c1-900 ;;
-    prof)   (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$arg -o $arg -- python $GRAFT_REPO_ROOT/bench.py --model $arg --no-secondary --no-cpu-baseline --no-sam --max-windows 2 --steps 5 --warmup 5 > $O/prof_$arg.log 2>&1); f=$(find $O/prof_$arg -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f $O/${arg}_rocprofv3_kernel_stats.csv && head -12 $f | cut -c1-200; t=$(find $O/prof_$arg -name '*kernel_trace.csv' | head -1); [ -n "$t" ] && python scripts/trace_compact.py $t > $O/${arg}_kernel_trace_compact.csv; rm -rf $O/prof_$arg ;;      # (raw traces: tens of MiB each, the merge-back limit is 64 MiB)
+    prof)   (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$arg -o $arg -- python $OLDPWD/bench.py --full --model $arg --no-secondary --no-cpu-baseline --no-sam --max-windows 2 --steps 5 --warmup 5 > $O/prof_$arg.log 2>&1); f=$(find $O/prof_$arg -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f $O/${arg}_rocprofv3_kernel_stats.csv && head -12 $f | cut -c1-200; t=$(find $O/prof_$arg -name '*kernel_trace.csv' | head -1); [ -n "$t" ] && python scripts/trace_compact.py $t > $O/${arg}_kernel_trace_compact.csv; rm -rf $O/prof_$arg ;;      # (raw traces: tens of MiB each, the merge-back limit is 64 MiB)
     pmc)    # HBM traffic: separate FETCH_SIZE / WRITE_SIZE passes of the eager step, folded per kernel family (MI355X_MICROARCH.md corrections)
       for c in FETCH_SIZE WRITE_SIZE; do
         (cd /tmp && timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$arg -o $c -- python $GRAFT_REPO_ROOT/bench.py --model $arg --steps 2 --warmup 1 --eager --no-cpu-baseline --no-secondary --no-sam --no-power --no-kernel-timer --max-windows 1 > $O/pmc_${arg}_$c.log 2>&1); echo "pmc $arg $c rc=$?"

@@ -13,9 +13,9 @@ timeout 600 python scripts/linear_fused_bench.py > $O/lab_default.jsonl 2>> $O/l
 echo "lab default picker: $(tail -1 $O/lab_default.jsonl | cut -c1-400)"
 for rep in 1 2; do
 for lib in - t22 t22m32; do
-  SAICV_NT_TILE=0 timeout 600 python scripts/with_lib.py $lib bench.py --model vit_base_patch16 --no-secondary --no-cpu-baseline --no-sam --max-windows 2 > $O/vit_tile0_${lib}_$rep.log 2>&1
+  SAICV_NT_TILE=0 timeout 600 python scripts/with_lib.py $lib bench.py --full --model vit_base_patch16 --no-secondary --no-cpu-baseline --no-sam --max-windows 2 > $O/vit_tile0_${lib}_$rep.log 2>&1
   echo "vit tile0 lib [$lib] rep $rep: $(tail -1 $O/vit_tile0_${lib}_$rep.log | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["value"], d.get("kernel_breakdown_ms_per_step"), d.get("power"))' 2>&1 | cut -c1-400)"
 done
 done
-timeout 600 python bench.py --model vit_base_patch16 --no-secondary --no-cpu-baseline --no-sam --max-windows 2 > $O/vit_default.log 2>&1
+timeout 600 python bench.py --full --model vit_base_patch16 --no-secondary --no-cpu-baseline --no-sam --max-windows 2 > $O/vit_default.log 2>&1
 echo "vit default: $(tail -1 $O/vit_default.log | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d["value"], d.get("kernel_breakdown_ms_per_step"))' 2>&1 | cut -c1-400)"

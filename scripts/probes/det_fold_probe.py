@@ -50,7 +50,7 @@ if __name__ == '__main__':
         line = [l for l in c.stdout.splitlines() if l.startswith('{')]
         print(line[-1] if line else c.stderr[-1200:], flush=True)
         seen[fold] = json.loads(line[-1])['colsum'] if line else None
-        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--model', 'resnet50', '--deterministic', '--no-secondary', '--no-cpu-baseline',
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--model', 'resnet50', '--deterministic', '--no-secondary', '--no-cpu-baseline',
                             '--no-sam', '--max-windows', '2'], env=env, capture_output=True, text=True)
         try:
             d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -60,7 +60,7 @@ if __name__ == '__main__':
             print('bench failed', fold, e, r.stderr[-800:], flush=True)
     print('statistics folds bit-equal between chain and default:', seen['chain'] is not None and seen['chain'] == seen['default'], flush=True)
     env = dict(os.environ)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--model', 'resnet50', '--no-secondary', '--no-cpu-baseline', '--no-sam',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--atomics', '--model', 'resnet50', '--no-secondary', '--no-cpu-baseline', '--no-sam',
                         '--max-windows', '2', '--steps', '20'], env=env, capture_output=True, text=True)
     d = json.loads(r.stdout.strip().splitlines()[-1])
     print(json.dumps({'fold': 'fast mode', 'ms_per_step': d['ms_per_step'], 'final_loss': d['config']['final_loss']}), flush=True)

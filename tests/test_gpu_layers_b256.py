@@ -18,6 +18,14 @@ import torch.nn.functional as F
 
 from conftest import rel_err
 
+
+@pytest.fixture(autouse=True)
+def _restore_threads():
+    """The oracle's thread count must not outlive the test: later CPU tests compare fp32 sums whose order depends on it."""
+    n = torch.get_num_threads()
+    yield
+    torch.set_num_threads(n)
+
 pytestmark = pytest.mark.gpu
 
 BATCH = int(os.environ.get('SAICV_TEST_BATCH', '256'))
