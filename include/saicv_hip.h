@@ -101,7 +101,8 @@ int saicv_unpack_wgrad_s2d(const float* dw, int O, int I, int R, int S, int Cq, 
 int saicv_conv2d_stat_rows(const saicv_conv_desc* d);
 /* y = conv(x, wf) [+ bias]; optionally per-channel partial sum / sum-of-squares of y
  * ([rows][K] each) for the following BatchNorm.  ATen `convolution` under
- * ConvBnActBlock.forward, resnet.py:45-48.  out_f32: write y as fp32 (logits). */
+ * ConvBnActBlock.forward, resnet.py:45-48.  out_f32: write y as fp32 (logits).
+ * Statistics with out_f32 != 0 are refused (-1): saicv_conv2d_stat_rows sizes the launch with out_f32 = 0. */
 int saicv_conv2d_fwd(const saicv_conv_desc* d, const void* x, const void* wf, const float* bias,
                      void* y, int out_f32, float* stat_sum, float* stat_sq, void* stream);
 /* dx = conv_transpose(dy, w) via Wd[C][R][S][K]   (`convolution_backward`, grad_input) */

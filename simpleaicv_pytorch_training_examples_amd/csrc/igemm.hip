@@ -22,6 +22,7 @@
 #include "common.h"
 #include "saicv_internal.h"
 #include "det.h"
+#include "../../include/saicv_hip.h"
 
 namespace {
 
@@ -37,15 +38,6 @@ DEVINL uint32_t fdiv(uint32_t n, FastDiv d) {
 // a CU so that one's epilogue overlaps the other's main loop
 constexpr int nt_stages(int bm, int bn) { return (bm == 256 && bn == 128) ? 3 : 4; }
 constexpr int nt_stages_kc8(int bm, int bn) { return (bm + bn) * 128 * 3 <= 150 * 1024 ? 3 : 2; }      // 128-byte K slices
-// resident workgroups per CU by LDS (the ring is all a workgroup holds: the epilogue stages through a vacated slot)
-// Which instantiations may run persistently (ticket draws hidden from the compiler, see draw_ticket): bf16 in and out,
-// and a register budget in which the compiler spills nothing -- a spilled ticket register would be saved before the atomic
-// has landed.  The 8-wavefront 256 x 128 geometry lives at 128 registers per lane (two workgroups per CU) and does spill
-// in its epilogue; it stays one tile per workgroup.  scripts/check_ticket_regs.py verifies the generated code of the rest.
-constexpr bool nt_can_persist(int elem_bytes, bool out_f32, int bm, int bn, int nwaves) {
-    return elem_bytes == 2 && !out_f32 && !(nwaves == 8 && bm * bn <= 256 * 128);
-}
-constexpr int nt_blocks_per_cu(int bm, int bn) { return 160 * 1024 / (nt_stages(bm, bn) * (bm + bn) * 64 + 16); }
 
 struct NTParams {
     const void* src;
@@ -74,9 +66,6 @@ struct NTParams {
     // rows (row = tile row mod count) of a zeroed buffer instead of written one row per tile row: few enough rows that the
     // consuming BatchNorm kernel finalises them itself (no partial-reduce / finalize launches)
     int stat_atomic_rows;
-    unsigned int* tickets;      // persistent launch: 8 per-XCD ticket counters (+ a departure counter at [32]), zero between launches
-    int stagger_phases;         // persistent launch: workgroups start in this many phase groups ...
-    int stagger_sleeps;         // ... `s_sleep 16` periods (~0.5 us each) apart, so that their epilogue store bursts interleave
     uint32_t src_bytes, wgt_bytes;
     int H, W, C;        // gather-source spatial dims / channels
     int OH, OW;         // pixel grid that indexes the GEMM rows
@@ -85,7 +74,6 @@ struct NTParams {
     int ldo;
     int tiles_n;
     int nblk;
-    int grid_x;         // resident workgroups (256 CUs x workgroups per CU)
     int kc8;            // host: launch the 128-byte-K-slice instantiation (pointwise bf16, 256-row tiles)
     int stream_out;     // host: the output is written with streaming stores (see NT_OUT_ST)
     FastDiv fd_ohw, fd_ow;   // for OH*OW and OW (unit-stride row decomposition)
@@ -171,758 +159,24 @@ template <int N> DEVINL void lgkm_release(u32x4& a, u32x4& b) { asm volatile("s_
 // 64 x 64 wavefront tile fed from LDS sustains 1 622 TFLOP/s at that limit on the 32 x 32 shape against 1 418 on 16x16x32
 // (scripts/probes/mfma_power_probe.hip).  What the models said, same box, library A/B (profiles/r05_nt_experiments.md): ViT-B 40.37 ->
 // 41.19 ms, ResNet-50 22.0 -> 22.2 ms with the 32 x 32 shape -- it moves twice the accumulator registers per flop (16 read + 16
-// written per K = 16) and the real loop, unlike the probe's, was never issue-bound.  16x16x32 stays; -DSAICV_NT_MFMA32 builds the other
-// (scripts/build_variant_lib.py).  32 x 32 fragments are the two 16-byte chunks (lane >> 5) of one 32-byte half of a 64-byte LDS row: the DMA
-// image and its XOR swizzle are unchanged and stay conflict free (the 16-lane groups of ds_read_b128 still meet all four swizzle
-// classes); C/D value r of a lane is column lane & 31 (second operand), row 8 * (r / 4) + 4 * (lane >> 5) + r % 4 (first operand).
+// written per K = 16) and the real loop, unlike the probe's, was never issue-bound.  16x16x32 stays (the 32 x 32 form: DESIGN.md).
 // fp32 (parity mode): 16x16x4, four per 16-byte chunk.
 template <typename T> struct NtMma;
-#ifdef SAICV_NT_MFMA32
-template <> struct NtMma<bf16_t> {
-    static constexpr int FR = 32, NV = 16, KSUB = 2;        // fragment rows, accumulator values per lane, MFMAs per 64-byte row
-    typedef f32x16 Acc;
-    static DEVINL void run(Acc& acc, const u32x4& a, const u32x4& b) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-    }
-};
-#else
 template <> struct NtMma<bf16_t> {
     static constexpr int FR = 16, NV = 4, KSUB = 1;
     typedef f32x4 Acc;
     static DEVINL void run(Acc& acc, const u32x4& a, const u32x4& b) { Mma<bf16_t>::run(acc, a, b); }
 };
-#endif
 template <> struct NtMma<float> {
     static constexpr int FR = 16, NV = 4, KSUB = 1;
     typedef f32x4 Acc;
     static DEVINL void run(Acc& acc, const u32x4& a, const u32x4& b) { Mma<float>::run(acc, a, b); }
 };
 
-// Main loop = LDS-DMA ring: `buffer_load ... lds` writes global chunks straight into an NSTAGE-slot LDS ring (no staging
-// registers, no ds_write), NSTAGE-1 K tiles are in flight across the single raw s_barrier of each K step, and the wait is
-// a COUNTED s_waitcnt vmcnt(N) that only retires the tile about to be consumed (guide section 5, T3/T4).  The DMA
-// destination is wave-linear (base + lane*16), so the XOR swizzle is applied to the SOURCE: lane l fetches the chunk that
-// belongs in the slot it will fill.
-// The loop is bound by MFMA issue only if the integer work per K tile is tiny, so:
-//  * all gathers are raw buffer loads: an out-of-range lane (padding halo, M/N/K tails) gets
-//    an offset beyond the buffer and the hardware writes zeros -- no branches, no exec masking;
-//  * the (r, s, c) position of a thread's K chunk advances incrementally (no divisions);
-//  * per-row constants fold image base and top-left corner, so a gather address is one add;
-//  * LDS fragment addresses (with the XOR swizzle) are computed once.
-// PLAIN: 1x1 taps without padding (pointwise conv, nn.Linear and their data-gradients): the K
-// index IS the channel offset, no tap walker and no halo tests in the loop.
-// Tile geometry (BM_T x BN_T output tile, WM_ x WN_ wavefronts, each owning a (BM_T/WM_) x (BN_T/WN_) sub-tile).
-//
-// r03 -- ONE OPERAND STREAM PER WORKGROUP, ACROSS TILES.  Round 2 measured a fixed cost of 10-12 us per output tile next
-// to ~1 us per K step (kernel exit, dispatch of the next workgroup, kernel-argument loads, index set-up, the first DMA's
-// HBM latency, a workgroup-wide LDS-staged epilogue): 30 % of a ViT-B K = 768 tile, 36 % of a 64-channel 3 x 3 one.  Now:
-//  * a launch with more tiles than resident workgroups is PERSISTENT: a workgroup draws its next tile from a per-XCD
-//    ticket counter (the tiles of one XCD stay a contiguous, L2-sharing range; late or slow workgroups simply draw fewer
-//    tickets, so nothing depends on all of them being resident -- RCCL kernels may hold CU slots);
-//  * the DMA stream does not drain at a tile boundary: the K steps of the NEXT tile are issued into the ring while the
-//    last steps of the current one are computed (the per-row gather state lives in the same registers -- it is
-//    recomputed at the switch, NSTAGE-1 steps before the compute side follows);
-//  * the epilogue is PER WAVEFRONT and needs no LDS of its own: a wavefront stages 16 rows of its sub-tile at a time
-//    through its share of the ring slot the last K step just vacated, reads them back as 16-byte row chunks (whole 128-byte
-//    lines per row in HBM) and stores them; no workgroup barrier, the next tile's operands are landing meanwhile;
-//  * BatchNorm statistics of bf16 outputs still come from the staged rows on the matrix cores (16x16x16: one transposed
-//    LDS read per 16 rows x 16 columns; sum = 1 . Y, sum of squares = diag(Y^T . Y)), per wavefront.
-// vmcnt accounting across the seam: gfx9 returns vector-memory operations in issue order (loads, stores and atomics share
-// the counter), so "at most LPT x min(2, steps issued after this one) operations outstanding" retires the K step about to
-// be consumed whatever epilogue stores or side loads were issued in between: they only make the wait conservative.
-// FUSEDK: the instantiation carries the fused epilogue modes (residual / drop-path / GELU / gated shortcut / BatchNorm-backward
-// sums, unaligned rows) -- or only the plain copy-out with BN statistics and bias.  Two kernels instead of two paths in one:
-// the plain one stays clear of the register cap (no spill reloads, i.e. no compiler vmcnt(0), around the tile seam) and can
-// count its own stores exactly.
-template <typename T, int BM_T, int BN_T, int WM_, int WN_, int MODE, bool OUT_F32, bool PLAIN, bool FUSEDK>
-__global__ __launch_bounds__(64 * WM_ * WN_, nt_blocks_per_cu(BM_T, BN_T) * WM_ * WN_ / 4)
-void igemm_nt_kernel(const NTParams p) {
-    constexpr int EPC = ElemTraits<T>::EPC;
-    constexpr int BK = 4 * EPC;                  // one 64-byte row per K tile
-    constexpr int NWAVES = WM_ * WN_;
-    constexpr int WMR = BM_T / WM_;              // rows of the output tile owned by one wavefront
-    constexpr int WN = BN_T / WN_;
-    constexpr int NT_ = WN / 16;
-    constexpr int MT_ = WMR / 16;
-    constexpr int AROWS = BM_T / 16 / NWAVES;    // A-tile DMA instructions per thread
-    constexpr int WROWS = BN_T / 16 / NWAVES;    // weight-tile DMA instructions per thread
-    constexpr int LPT = AROWS + WROWS;           // loads per thread per K tile
-    constexpr int NSTAGE = nt_stages(BM_T, BN_T);
-    constexpr int A_BYTES = BM_T * 64;
-    constexpr int W_BYTES = BN_T * 64;
-    constexpr int STAGE = A_BYTES + W_BYTES;
-    constexpr int MBOX = NSTAGE * STAGE;         // one dword behind the ring: the tile after the one being streamed
-    constexpr uint32_t OOB = 0xfffffff0u;        // 16-byte aligned, beyond any operand (host checks sizes)
-    static_assert(AROWS >= 1 && WROWS >= 1, "every wavefront issues at least one DMA row block per operand");
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform (LDS-DMA base)
-    const int wm = wave % WM_;
-    const int wn = wave / WM_;
-
-    // ---- data-gradient with stride s > 1: the input pixels split into s*s parity classes
-    // (h % s, w % s); a class only ever meets the taps r == (h + pad) mod s, so each class is a
-    // dense GEMM over its own tap subset (no multiply-by-zero work).  blockIdx.y = class.
-    // In class-local terms the source pixel of (row, tap) is (A0 - tr, B0 - ts).
-    int cs = 1, ph = 0, pw = 0, r0 = 0, s0 = 0, q0h = p.pad, q0w = p.pad;
-    int Sc = p.S, Hc = p.OH, Wc = p.OW, Mc = p.M, Kc = p.Kd;
-    int nblk = p.nblk;
-    if (MODE == 1 && p.stride > 1) {
-        cs = p.stride;
-        ph = blockIdx.y / cs;
-        pw = blockIdx.y - ph * cs;
-        Hc = (p.OH - ph + cs - 1) / cs;
-        Wc = (p.OW - pw + cs - 1) / cs;
-        Mc = (p.M / (p.OH * p.OW)) * Hc * Wc;
-        r0 = (ph + p.pad) % cs;
-        s0 = (pw + p.pad) % cs;
-        q0h = (ph + p.pad - r0) / cs;
-        q0w = (pw + p.pad - s0) / cs;
-        const int Rc = r0 < p.R ? (p.R - r0 + cs - 1) / cs : 0;
-        Sc = s0 < p.S ? (p.S - s0 + cs - 1) / cs : 0;
-        Kc = Rc * Sc * p.C;
-        nblk = ((Mc + BM_T - 1) / BM_T) * p.tiles_n;
-    }
-    const int ohw = Hc * Wc;
-    const int nkt = (Kc + BK - 1) / BK;          // 0 for a class without taps: the output is zero
-
-    // ---- which tiles: block b runs on XCD b % 8 (observed dispatch order; speed only) and XCD x owns the contiguous tile
-    // range [xbase, xbase + xcount): its workgroups take the first gridDim.x / 8 of them by position, the rest by ticket
-    constexpr bool CAN_PERSIST = nt_can_persist((int)sizeof(T), OUT_F32, BM_T, BN_T, NWAVES);
-    const bool persistent = CAN_PERSIST && p.tickets != nullptr;      // host: only with more tiles than workgroups and nkt > NSTAGE
-    const int xcd = blockIdx.x & 7;
-    const int xq = nblk >> 3, xr = nblk & 7;
-    const int xbase = (xcd < xr) ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq;
-    const int xcount = xq + (xcd < xr ? 1 : 0);
-    const int xwg = (int)(gridDim.x >> 3) + (((int)(gridDim.x & 7) > xcd) ? 1 : 0);     // workgroups of this launch on this XCD
-    unsigned int* const ticket = persistent ? p.tickets + blockIdx.y * 8 + xcd : nullptr;
-    const int pos0 = (int)(blockIdx.x >> 3);
-    const int first = pos0 < xcount ? xbase + pos0 : -1;
-
-    const __amdgpu_buffer_rsrc_t src_rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.src), 0, p.src_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wgt_rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wgt), 0, p.wgt_bytes, 0x00020000);
-
-    // ---- per-thread DMA state of the tile being streamed.  Wave w, instruction i, lane l fills LDS bytes
-    // [(i*NWAVES + w)*1024 + l*16, +16) of the A region: row (i*NWAVES+w)*16 + (l>>2), slot l&3, i.e. the
-    // logical chunk (l&3) ^ f((row>>2)&3) = (l&3) ^ f((l>>4)&3) -- one K-chunk column per thread.
-    const int cc = (lane & 3) ^ lds_swz((lane >> 4) & 3);
-    int rowc[AROWS], a0[AROWS], b0[AROWS];   // rowc = (image base + A0*W + B0) * C  [elements]
-    int wrow[WROWS];                         // weight row base [elements], or -1
-    int kpos = 0, tc0 = 0, ttr = 0, tts = 0; // K-chunk walker: k = kt*BK + cc*EPC  ->  (tr, ts, c0), advanced by BK per tile
-#pragma unroll
-    for (int i = 0; i < AROWS; ++i) { rowc[i] = 0; a0[i] = 0; b0[i] = 0; }      // (defined on every path: the arrays stay in registers)
-#pragma unroll
-    for (int j = 0; j < WROWS; ++j) wrow[j] = -1;
-    auto stream_tile = [&](int bid) __attribute__((always_inline)) {        // point the DMA state at the first K step of tile `bid`
-        const int tile_n = bid % p.tiles_n;
-        const int tile_m = bid / p.tiles_n;
-#pragma unroll
-        for (int i = 0; i < AROWS; ++i) {
-            const int mq = tile_m * BM_T + (i * NWAVES + wave) * 16 + (lane >> 2);
-            const bool in = mq < Mc;
-            const int m = in ? mq : 0;          // branch-free: rows past the end decompose row 0 and are then marked out of range
-            int img, oh, ow;
-            if (cs == 1) {
-                img = (int)fdiv((uint32_t)m, p.fd_ohw);
-                const int rem = m - img * ohw;
-                oh = (int)fdiv((uint32_t)rem, p.fd_ow);
-                ow = rem - oh * Wc;
-            } else {
-                img = m / ohw;
-                const int rem = m - img * ohw;
-                oh = rem / Wc;
-                ow = rem - oh * Wc;
-            }
-            const int av = MODE == 0 ? oh * p.stride - p.pad : oh + q0h;
-            const int bv = MODE == 0 ? ow * p.stride - p.pad : ow + q0w;
-            a0[i] = in ? av : -(1 << 24);
-            b0[i] = in ? bv : -(1 << 24);
-            rowc[i] = in ? ((img * p.H + av) * p.W + bv) * p.C : 0;
-        }
-#pragma unroll
-        for (int j = 0; j < WROWS; ++j) {
-            const int n = tile_n * BN_T + (j * NWAVES + wave) * 16 + (lane >> 2);
-            wrow[j] = n < p.Nn ? n * p.Kd : -1;
-        }
-        kpos = cc * EPC;
-        const int tap = kpos / p.C;
-        tc0 = kpos - tap * p.C;
-        ttr = Sc > 0 ? tap / Sc : 0;
-        tts = tap - ttr * Sc;
-    };
-
-    typedef __attribute__((address_space(3))) void lds_void;
-    // issue the DMA of the next K tile (walker position) into ring slot `stage`
-    auto issue_tile = [&](int stage) __attribute__((always_inline)) {
-        char* base = smem + stage * STAGE + wave * 1024;
-        const bool kvalid = kpos < Kc;
-        int tapoff, kw;
-        if (PLAIN) {
-            tapoff = kpos;
-            kw = kpos;
-        } else if (MODE == 0) {
-            tapoff = (ttr * p.W + tts) * p.C + tc0;
-            kw = kpos;
-        } else {
-            tapoff = tc0 - (ttr * p.W + tts) * p.C;
-            kw = ((r0 + ttr * cs) * p.S + (s0 + tts * cs)) * p.C + tc0;
-        }
-#pragma unroll
-        for (int i = 0; i < AROWS; ++i) {
-            const int ih = PLAIN ? a0[i] : (MODE == 0) ? a0[i] + ttr : a0[i] - ttr;
-            const int iw = PLAIN ? b0[i] : (MODE == 0) ? b0[i] + tts : b0[i] - tts;
-            // bitwise (not short-circuit) logic keeps this branch-free
-            const bool ok = PLAIN ? (kvalid & (a0[i] >= 0))
-                                  : (kvalid & ((unsigned)ih < (unsigned)p.H) & ((unsigned)iw < (unsigned)p.W));
-            const uint32_t off = ok ? (uint32_t)(rowc[i] + tapoff) * (uint32_t)sizeof(T) : OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(src_rs, (lds_void*)(base + i * NWAVES * 1024), 16, (int)off, 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < WROWS; ++j) {
-            const bool ok = kvalid & (wrow[j] >= 0);
-            const uint32_t off = ok ? (uint32_t)(wrow[j] + kw) * (uint32_t)sizeof(T) : OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wgt_rs, (lds_void*)(base + A_BYTES + j * NWAVES * 1024), 16, (int)off, 0, 0, 0);
-        }
-        // advance to the next K tile
-        kpos += BK;
-        if (PLAIN) return;
-        tc0 += BK;
-        if (p.C >= BK) {                 // at most one tap boundary per tile (uniform branch)
-            const bool wrap = tc0 >= p.C;
-            tc0 -= wrap ? p.C : 0;
-            tts += wrap ? 1 : 0;
-            const bool wrap2 = tts == Sc;
-            tts = wrap2 ? 0 : tts;
-            ttr += wrap2 ? 1 : 0;
-        } else {
-            while (tc0 >= p.C) {
-                tc0 -= p.C;
-                if (++tts == Sc) { tts = 0; ++ttr; }
-            }
-        }
-    };
-
-    f32x4 acc[NT_][MT_];
-#pragma unroll
-    for (int ni = 0; ni < NT_; ++ni)
-#pragma unroll
-        for (int mi = 0; mi < MT_; ++mi) acc[ni][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int l15 = lane & 15;
-    const int lg = lane >> 4;
-    int fa[MT_], fw[NT_];               // LDS fragment offsets within a stage, hoisted out of the K loop (not out of the tile
-                                        // loop: they are recomputed per tile so that they are not live across the epilogue)
-    auto fragment_offsets = [&]() __attribute__((always_inline)) {
-        int l15o = l15, lgo = lg;
-        asm volatile("" : "+v"(l15o), "+v"(lgo));       // opaque: keeps the compiler from hoisting the offsets over the epilogue
-#pragma unroll
-        for (int mi = 0; mi < MT_; ++mi) fa[mi] = lds_off(wm * WMR + mi * 16 + l15o, lgo);
-#pragma unroll
-        for (int ni = 0; ni < NT_; ++ni) fw[ni] = A_BYTES + lds_off(wn * WN + ni * 16 + l15o, lgo);
-    };
-
-    auto compute = [&](int stage) __attribute__((always_inline)) {
-        const char* base = smem + stage * STAGE;
-        u32x4 af[MT_], wf[NT_];
-#pragma unroll
-        for (int mi = 0; mi < MT_; ++mi) af[mi] = ld_chunk(base + fa[mi]);
-#pragma unroll
-        for (int ni = 0; ni < NT_; ++ni) wf[ni] = ld_chunk(base + fw[ni]);
-#pragma unroll
-        for (int ni = 0; ni < NT_; ++ni)
-#pragma unroll
-            for (int mi = 0; mi < MT_; ++mi) Mma<T>::run(acc[ni][mi], wf[ni], af[mi]);
-    };
-
-    // ---- the operand stream.  bid_i / ki: tile and K step the DMA side is at; the mailbox holds the tile after bid_i
-    // (written by wavefront 0 two K steps after it drew the ticket, read by everyone at the switch, >= 1 barrier later).
-    int bid_c = first;                 // tile being computed
-    int bid_i = first, ki = 0;
-    int issued = 0, consumed = 0;      // K steps issued / retired by this workgroup, over all its tiles
-    int st_i = 0, st_c = 0;            // ring slots of the next DMA / the step being consumed
-    unsigned int tk = 0u;              // wavefront 0, lane 0: the ticket in flight
-    bool mb_pending = false;
-    int mb_wait = 0;
-    // The ticket is drawn ASYNCHRONOUSLY: a returning atomic hidden from the compiler (atomicAdd() is followed by an
-    // immediate s_waitcnt vmcnt(0) -- the whole DMA ring plus an L2 round trip, once per tile), whose result lands in `tk`
-    // some time later.  It is read two K steps on, behind the counted vmcnt wait of that step: vector-memory operations
-    // return in issue order and that wait leaves at most 2 x LPT of them outstanding, all issued after the atomic.
-    // The compiler does not know `tk` is in flight: tests/test_kernel_asm.py checks in the generated code of every
-    // instantiation that nothing reads or copies the destination register before the mailbox write.
-    const uint32_t mbox_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)(smem + MBOX);
-    auto draw_ticket = [&]() __attribute__((always_inline)) {
-        if constexpr (CAN_PERSIST) {
-            if (wave == 0 && lane == 0) {
-                const unsigned int one = 1u;
-                asm volatile("global_atomic_add %0, %1, %2, off sc0 ; saicv ticket" : "=v"(tk) : "v"(ticket), "v"(one) : "memory");
-            }
-            mb_pending = true;
-        }
-    };
-    auto issue_next = [&]() __attribute__((always_inline)) {
-        if (bid_i < 0) return;
-        if (ki == nkt) {               // the stream moves on to the next tile of this workgroup
-            int nb = -1;
-            if (CAN_PERSIST && persistent) {
-                int v;              // LDS access spelled out: a volatile generic access becomes a FLAT load behind vmcnt(0)
-                asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(mbox_addr) : "memory");
-                nb = __builtin_amdgcn_readfirstlane(v);
-            }
-            bid_i = nb;
-            ki = 0;
-            if (bid_i < 0) return;
-            stream_tile(bid_i);
-            draw_ticket();
-            mb_wait = 1;
-        }
-        issue_tile(st_i);
-        ++ki;
-        ++issued;
-        st_i = (st_i + 1 == NSTAGE) ? 0 : st_i + 1;
-    };
-    // ---- staggered start.  Tiles of one launch take the same time, so workgroups that start together reach their epilogues
-    // together: 256 x 128 KiB of output stores hit HBM at once (33 MB, ~7 us at 4.7 TB/s) while every matrix core idles --
-    // and gfx9 returns vector-memory operations in issue order, so a wavefront cannot confirm the operand loads it issued
-    // BEHIND its stores before those stores are acknowledged (r03 measurement: a ViT-B K = 768 tile computes in ~22 us and
-    // then waits ~7 us).  A persistent workgroup keeps the phase it starts with; spreading the starts over a tile period in
-    // a few groups turns the bursts into a steady write stream that the next tile's first K steps cover.
-    if (persistent && p.stagger_phases > 1) {
-        const int slot = (int)(blockIdx.x >> 3) + (int)(blockIdx.x >> 8) * (p.stagger_phases >> 1);   // b and b + 256 share a CU
-        const int naps = (slot % p.stagger_phases) * p.stagger_sleeps;
-        for (int i = 0; i < naps; ++i) __builtin_amdgcn_s_sleep(16);
-    }
-    if (bid_c >= 0) {
-        stream_tile(bid_i);
-        if (persistent) draw_ticket();
-        if (nkt > 0)
-            for (int s = 0; s < NSTAGE - 1; ++s) issue_next();
-    }
-
-    typedef typename std::conditional<OUT_F32, float, T>::type TO;
-    // ---- epilogue geometry (per wavefront): a "piece" = 16 rows x WNS columns of the sub-tile, staged in LDS with a
-    // padded pitch, read back as 16-byte row chunks: CPR chunks per row, CPL per lane, lane -> (row = j*RPJ + lane/CPR,
-    // chunk = lane % CPR) -- a lane's column chunk is the same for every row it touches
-    constexpr int SLOT_SHARE = STAGE / NWAVES;
-    constexpr int NSPLIT = (16 * (WN * (int)sizeof(TO) + 16) <= SLOT_SHARE) ? 1 : 2;     // column halves per piece (fp32 outputs)
-    constexpr int NTH = NT_ / NSPLIT;
-    constexpr int WNS = WN / NSPLIT;
-    constexpr int OPITCH = WNS * (int)sizeof(TO) + 16;          // bytes; +16 staggers banks
-    static_assert(16 * OPITCH <= SLOT_SHARE && NT_ % NSPLIT == 0, "the staged piece must fit this wavefront's share of a ring slot");
-    constexpr int OEPC = 16 / (int)sizeof(TO);
-    constexpr int CPR = WNS / OEPC;
-    constexpr int CPL = (16 * CPR) / 64;
-    constexpr int RPJ = 64 / CPR;                               // rows covered by one chunk pass of the wavefront
-    static_assert(16 * CPR >= 64 && CPL * 64 == 16 * CPR, "a staged piece is a whole number of chunk passes of the wavefront");
-    constexpr bool MSTAT = !OUT_F32 && sizeof(T) == 2 && MODE == 0;      // BN statistics from the staged bf16 rows (matrix cores)
-    constexpr bool VSTAT = MODE == 0 && !MSTAT;                          // ... from the accumulators (fp32 outputs)
-    constexpr bool DGRAD_EXTRAS = MODE == 1 && sizeof(TO) == sizeof(T);  // gated shortcut / BatchNorm-backward sums: data gradient only
-    TO* const outp = reinterpret_cast<TO*>(p.out);
-    const bool aligned = ((p.ldo * (int)sizeof(TO)) & 15) == 0;
-    const bool remap = MODE == 1 && cs > 1;
-    const bool do_stats = MODE == 0 && p.stat_sum != nullptr;
-    const bool bstats = DGRAD_EXTRAS && p.bs_y != nullptr;
-    const bool addp = p.addend != nullptr, scalep = p.row_scale != nullptr;
-    const bool gatep = DGRAD_EXTRAS && p.addend_gate != nullptr, maskp = bstats && p.bs_mask != nullptr;
-    const bool fused = p.act_mode != 0 || addp || scalep || bstats;
-    const bool fast = aligned && !remap && !fused;             // plain copy-out of whole chunks (N tail checked per chunk)
-
-    auto epilogue = [&](int bid, char* stg) __attribute__((always_inline)) {
-        // lane-derived indices of the epilogue are recomputed per tile from an opaque copy of the lane id: hoisted out of the
-        // tile loop they would sit in registers all through the main loop (the 256-wide geometries run at the 256-register cap)
-        int lane_o = lane;
-        asm volatile("" : "+v"(lane_o));
-        const int l15 = lane_o & 15;
-        const int lg = lane_o >> 4;
-        const int crow = lane_o / CPR;                                  // row of this lane's chunk within a pass
-        const int ccol = lane_o % CPR;                                  // its chunk column
-        const int tile_n = bid % p.tiles_n;
-        const int tile_m = bid / p.tiles_n;
-        const int m_base = tile_m * BM_T + wm * WMR;
-        const int n_base = tile_n * BN_T + wn * WN;
-        float ssum[NT_][4], ssq[NT_][4];                   // VSTAT: column sums from the accumulators
-        float msum[NT_], msq[NT_];                          // MSTAT: this lane's column (sum: lanes lg == 0; squares: lg == l15 >> 2)
-        float bag[NSPLIT][OEPC], bax[NSPLIT][OEPC];         // BatchNorm-backward sums of this lane's column chunk
-#pragma unroll
-        for (int ni = 0; ni < NT_; ++ni) {
-            msum[ni] = 0.f; msq[ni] = 0.f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { ssum[ni][r] = 0.f; ssq[ni][r] = 0.f; }
-        }
-#pragma unroll
-        for (int h = 0; h < NSPLIT; ++h)
-#pragma unroll
-            for (int e = 0; e < OEPC; ++e) { bag[h][e] = 0.f; bax[h][e] = 0.f; }
-        if (MODE == 0 && p.bias != nullptr) {      // (uniform) the bias joins the accumulators before they are staged: no bias
-#pragma unroll                                     // registers live across the piece loop
-            for (int ni = 0; ni < NT_; ++ni) {
-                const int n = n_base + ni * 16 + lg * 4;
-                const f32x4 bv = {n < p.Nn ? p.bias[n] : 0.f, n + 1 < p.Nn ? p.bias[n + 1] : 0.f,
-                                  n + 2 < p.Nn ? p.bias[n + 2] : 0.f, n + 3 < p.Nn ? p.bias[n + 3] : 0.f};
-#pragma unroll
-                for (int mi = 0; mi < MT_; ++mi) acc[ni][mi] += bv;
-            }
-        }
-        // accumulators of row block MI (static index) + bias -> this wavefront's staging rows, columns of half H
-        auto stage_rows = [&](auto MI, auto H) __attribute__((always_inline)) {
-            constexpr int mi = decltype(MI)::value, h = decltype(H)::value;
-#pragma unroll
-            for (int i = 0; i < NTH; ++i) {
-                const int ni = h * NTH + i;
-                float v[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = acc[ni][mi][r];
-                if (VSTAT) {
-                    if (do_stats) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float vr = OUT_F32 ? v[r] : round_through<T>(v[r]);
-                            ssum[ni][r] += vr;
-                            ssq[ni][r] = fmaf(vr, vr, ssq[ni][r]);
-                        }
-                    }
-                }
-                char* q = stg + l15 * OPITCH + (i * 16 + lg * 4) * (int)sizeof(TO);
-                if (sizeof(TO) == 2) {
-                    bf16x4 pk;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)v[r];
-                    *reinterpret_cast<bf16x4*>(q) = pk;
-                } else {
-                    *reinterpret_cast<f32x4*>(q) = f32x4{v[0], v[1], v[2], v[3]};
-                }
-            }
-        };
-        // The piece loop exists twice: FUSED = false is the plain copy-out (no global load anywhere in it, so the compiler has
-        // no load destinations to protect with s_waitcnt vmcnt(0) -- which, with stores in flight, would be a store round
-        // trip per piece: gfx9 returns loads and stores in issue order), FUSED = true carries every fused mode.
-        auto pieces = [&](auto FUSED_T) __attribute__((always_inline)) {
-            constexpr bool FUSED = decltype(FUSED_T)::value;
-#pragma unroll 1
-            for (int mi = 0; mi < MT_; ++mi) {
-#pragma unroll
-                for (int h = 0; h < NSPLIT; ++h) {
-                    int mrow[CPL];
-                    u32x4 av[CPL], yv[CPL];
-                    unsigned gb[CPL], mb[CPL];
-                    float sc[CPL];
-                    const int ncol = n_base + h * WNS + ccol * OEPC;
-                    const bool col_in = ncol < p.Nn;
-                    const bool whole = aligned && ncol + OEPC <= p.Nn;
-#pragma unroll
-                    for (int j = 0; j < CPL; ++j) {
-                        const int mr = m_base + mi * 16 + j * RPJ + crow;           // row in tile-order (class-local) numbering
-                        int mo = (mr < Mc && col_in) ? mr : -1;
-                        if (FUSED && remap && mo >= 0) {
-                            const int img = mr / ohw;
-                            const int rem = mr - img * ohw;
-                            const int hc = rem / Wc;
-                            mo = (img * p.OH + hc * cs + ph) * p.OW + (rem - hc * Wc) * cs + pw;
-                        }
-                        mrow[j] = mo;
-                        av[j] = u32x4{0u, 0u, 0u, 0u};
-                        yv[j] = u32x4{0u, 0u, 0u, 0u};
-                        gb[j] = 0xffu;
-                        mb[j] = 0xffu;
-                        sc[j] = 1.f;
-                        if constexpr (FUSED) {
-                            // side operands of this piece's chunks: every global load in flight before the staging round trip
-                            if (fused && mo >= 0) {
-                                const size_t off = (size_t)mo * p.ldo + ncol;
-                                if (scalep) sc[j] = p.row_scale[mo / p.rows_per_scale];
-                                if (addp && whole) av[j] = ld_chunk(reinterpret_cast<const TO*>(p.addend) + off);
-                                if (bstats) yv[j] = ld_chunk(reinterpret_cast<const TO*>(p.bs_y) + off);
-                                if (gatep) gb[j] = p.addend_gate[off / OEPC];
-                                if (maskp) mb[j] = p.bs_mask[off / OEPC];
-                            }
-                        }
-                    }
-                    // ---- accumulators -> LDS (the only part that needs static register indices: one small case per row block)
-#define STAGE_CASE(K)                                                                                                       \
-                    if constexpr (MT_ > K) {                                                                                \
-                        if (mi == K) {                                                                                      \
-                            if (h == 0) stage_rows(std::integral_constant<int, K>{}, std::integral_constant<int, 0>{});     \
-                            if constexpr (NSPLIT == 2) {                                                                    \
-                                if (h == 1) stage_rows(std::integral_constant<int, K>{}, std::integral_constant<int, 1>{}); \
-                            }                                                                                               \
-                        }                                                                                                   \
-                    }
-                    STAGE_CASE(0) STAGE_CASE(1) STAGE_CASE(2) STAGE_CASE(3) STAGE_CASE(4) STAGE_CASE(5) STAGE_CASE(6) STAGE_CASE(7)
-#undef STAGE_CASE
-                    // ---- BatchNorm statistics of the staged bf16 rows on the matrix cores
-                    if constexpr (MSTAT) {
-                        if (do_stats) {
-                            typedef __attribute__((ext_vector_type(4))) short s16x4;
-                            const s16x4 ones = {(short)0x3f80, (short)0x3f80, (short)0x3f80, (short)0x3f80};
-                            // lane (column t = l15, row group lg) of a 16-lane group supplies the address of row lg*4 + (t>>2),
-                            // columns (t&3)*4.. and receives rows lg*4 .. lg*4+3 of column t: the B fragment of a 16x16x16 MFMA.
-                            // Spelled as asm: behind the BUILTIN transposed read the compiler waits vmcnt(0) (an LDS access it
-                            // can see, while LDS-DMA writes are pending) -- with the previous piece's stores in flight that is a
-                            // store round trip per piece.  LDS operations of one wavefront execute in issue order, so the staged
-                            // rows written just above are what these reads return.
-                            const uint32_t qa = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)(
-                                stg + (lg * 4 + (l15 >> 2)) * OPITCH + (l15 & 3) * 8);
-                            s16x4 ys[NTH];
-                            static_assert(NTH == 4 || NTH == 2, "column groups of a staged piece");
-                            if constexpr (NTH == 4) {
-                                asm volatile("ds_read_b64_tr_b16 %0, %4\n\tds_read_b64_tr_b16 %1, %4 offset:32\n\t"
-                                             "ds_read_b64_tr_b16 %2, %4 offset:64\n\tds_read_b64_tr_b16 %3, %4 offset:96\n\t"
-                                             "s_waitcnt lgkmcnt(0)"
-                                             : "=&v"(ys[0]), "=&v"(ys[1]), "=&v"(ys[2]), "=&v"(ys[3]) : "v"(qa) : "memory");
-                            } else {
-                                asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:32\n\t"
-                                             "s_waitcnt lgkmcnt(0)"
-                                             : "=&v"(ys[0]), "=&v"(ys[1]) : "v"(qa) : "memory");
-                            }
-#pragma unroll
-                            for (int i = 0; i < NTH; ++i) {
-                                const s16x4 y = ys[i];
-                                const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-                                const f32x4 s1 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ones, y, z, 0, 0, 0);
-                                const f32x4 s2 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(y, y, z, 0, 0, 0);
-                                // the diagonal element of this lane's column: row l15 = lg*4 + r lives in lanes lg == l15 >> 2.
-                                // (opaque copies: a select chain on vector elements is otherwise turned into a dynamically
-                                // indexed extract, which the backend lowers through scratch memory)
-                                float e0 = s2[0], e1 = s2[1], e2 = s2[2], e3 = s2[3];
-                                asm volatile("" : "+v"(e0), "+v"(e1), "+v"(e2), "+v"(e3));
-                                const int r = l15 & 3;
-                                msum[h * NTH + i] += s1[0];
-                                msq[h * NTH + i] += (r & 2) ? ((r & 1) ? e3 : e2) : ((r & 1) ? e1 : e0);
-                            }
-                        }
-                    }
-                    // ---- staged rows -> 16-byte row chunks -> (fused modes) -> HBM
-#pragma unroll
-                    for (int j = 0; j < CPL; ++j) {
-                        const int mo = mrow[j];
-                        u32x4 v = ld_chunk(stg + (j * RPJ + crow) * OPITCH + ccol * 16);
-                        if (mo < 0) continue;
-                        TO* o = outp + (size_t)mo * p.ldo + ncol;
-                        if constexpr (!FUSED) {
-                            if (whole) {
-                                st_chunk(o, v);
-                            } else {
-                                float e[OEPC];
-                                Chunk<TO>::unpack(v, e);
-#pragma unroll
-                                for (int k = 0; k < OEPC; ++k)
-                                    if (ncol + k < p.Nn) o[k] = from_f32<TO>(e[k]);
-                            }
-                        } else {
-                            float f[OEPC];
-                            Chunk<TO>::unpack(v, f);
-                            if (p.act_mode == 1 || p.act_mode == 3) {   // fc1 of an MLP: emit gelu() beside the pre-activation (1) or gelu'() (3)
-                                float gl[OEPC], gr[OEPC];
-                                gelu_and_grad8(f, gl, gr);
-                                st_chunk(reinterpret_cast<TO*>(p.out2) + (size_t)mo * p.ldo + ncol, Chunk<TO>::pack(gl));
-                                if (p.act_mode == 3) v = Chunk<TO>::pack(gr);
-                            } else if (p.act_mode == 2 || p.act_mode == 4) {     // dgrad of fc2: times gelu'(pre) (2) or times the stored derivative (4)
-                                float a[OEPC];
-                                Chunk<TO>::unpack(av[j], a);
-                                if (p.act_mode == 2) {
-#pragma unroll
-                                    for (int k = 0; k < OEPC; ++k) f[k] *= gelu_grad_f(a[k]);
-                                } else {
-#pragma unroll
-                                    for (int k = 0; k < OEPC; ++k) f[k] *= a[k];
-                                }
-                                v = Chunk<TO>::pack(f);
-                            } else if (addp || scalep) {
-                                float a[OEPC];
-                                if (whole) {
-                                    Chunk<TO>::unpack(av[j], a);
-                                } else {
-#pragma unroll
-                                    for (int k = 0; k < OEPC; ++k)
-                                        a[k] = (addp && ncol + k < p.Nn)
-                                                   ? to_f32(reinterpret_cast<const TO*>(p.addend)[(size_t)mo * p.ldo + ncol + k]) : 0.f;
-                                }
-#pragma unroll
-                                for (int k = 0; k < OEPC; ++k) f[k] = fmaf(sc[j], f[k], ((gb[j] >> k) & 1u) ? a[k] : 0.f);
-                                v = Chunk<TO>::pack(f);
-                            }
-                            if (bstats) {                     // BatchNorm-backward sums of what is stored (rounded to TO), behind its ReLU gate
-                                float yy[OEPC];
-                                Chunk<TO>::unpack(v, f);
-                                Chunk<TO>::unpack(yv[j], yy);
-#pragma unroll
-                                for (int k = 0; k < OEPC; ++k) {
-                                    const float ge = ((mb[j] >> k) & 1u) ? f[k] : 0.f;
-                                    bag[h][k] += ge;
-                                    bax[h][k] = fmaf(ge, yy[k], bax[h][k]);
-                                }
-                            }
-                            if (whole) {
-                                st_chunk(o, v);
-                            } else {                          // N tail, or a leading dimension without 16-byte alignment
-                                float e[OEPC];
-                                Chunk<TO>::unpack(v, e);
-#pragma unroll
-                                for (int k = 0; k < OEPC; ++k)
-                                    if (ncol + k < p.Nn) o[k] = from_f32<TO>(e[k]);
-                            }
-                        }
-                    }
-                }
-            }
-        };
-        if constexpr (FUSEDK) pieces(std::true_type{});
-        else pieces(std::false_type{});           // host: launched only when `fast` holds
-        // ---- statistics of this wavefront's rows: one partial row per (tile row, wavefront row), or atomics into a few rows
-        if (do_stats) {
-            const size_t srow = p.stat_atomic_rows ? (size_t)((tile_m * WM_ + wm) % p.stat_atomic_rows) : (size_t)(tile_m * WM_ + wm);
-            if constexpr (MSTAT) {
-#pragma unroll
-                for (int ni = 0; ni < NT_; ++ni) {
-                    const int n = n_base + ni * 16 + l15;              // D: row lg*4 + r, column l15
-                    if (n < p.Nn) {
-                        if (lg == 0) {
-                            if (p.stat_atomic_rows) unsafeAtomicAdd(&p.stat_sum[srow * (size_t)p.Nn + n], msum[ni]);
-                            else p.stat_sum[srow * (size_t)p.Nn + n] = msum[ni];
-                        }
-                        if (lg == (l15 >> 2)) {
-                            if (p.stat_atomic_rows) unsafeAtomicAdd(&p.stat_sq[srow * (size_t)p.Nn + n], msq[ni]);
-                            else p.stat_sq[srow * (size_t)p.Nn + n] = msq[ni];
-                        }
-                    }
-                }
-            }
-            if constexpr (VSTAT) {
-                // rows m >= M were gathered as zeros (no bias when stats are requested) -> add 0.
-#pragma unroll
-                for (int ni = 0; ni < NT_; ++ni)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {        // over the 16 pixel lanes: four DPP adds each
-                        const float a = row16_sum(ssum[ni][r]), b = row16_sum(ssq[ni][r]);
-                        const int n = n_base + ni * 16 + lg * 4 + r;
-                        if (l15 == 0 && n < p.Nn) {
-                            if (p.stat_atomic_rows) {
-                                unsafeAtomicAdd(&p.stat_sum[srow * (size_t)p.Nn + n], a);
-                                unsafeAtomicAdd(&p.stat_sq[srow * (size_t)p.Nn + n], b);
-                            } else {
-                                p.stat_sum[srow * (size_t)p.Nn + n] = a;
-                                p.stat_sq[srow * (size_t)p.Nn + n] = b;
-                            }
-                        }
-                    }
-            }
-        }
-        if (FUSEDK && bstats) {
-            // sum g * (y - mean) * invstd = invstd * (sum g y - mean * sum g): the mean leaves after this lane's few rows,
-            // while the sums are still small -- not after the whole column.  Lanes sharing a chunk column differ in crow.
-            const size_t prow0 = (size_t)((MODE == 1 && cs > 1) ? blockIdx.y : 0) * p.bs_rows + tile_m;
-            const size_t prow = prow0 * WM_ + wm;
-            const size_t drow = p.stat_atomic_rows ? prow % p.stat_atomic_rows : prow;
-#pragma unroll
-            for (int h = 0; h < NSPLIT; ++h) {
-                const int ncol = n_base + h * WNS + ccol * OEPC;
-                const bool have = ncol + OEPC <= p.Nn;
-#pragma unroll
-                for (int e = 0; e < OEPC; ++e) {
-                    const float mu = have ? p.bs_mean[ncol + e] : 0.f, is = have ? p.bs_invstd[ncol + e] : 0.f;
-                    float g = bag[h][e];
-                    float gx = is * fmaf(-mu, bag[h][e], bax[h][e]);
-#pragma unroll
-                    for (int d = CPR; d < 64; d <<= 1) {
-                        g += __shfl_xor(g, d, 64);
-                        gx += __shfl_xor(gx, d, 64);
-                    }
-                    if (lane_o < CPR && have) {
-                        float* dg = p.bs_g + drow * (size_t)p.Nn + ncol + e;
-                        float* dx = p.bs_gx + drow * (size_t)p.Nn + ncol + e;
-                        if (p.stat_atomic_rows) { unsafeAtomicAdd(dg, g); unsafeAtomicAdd(dx, gx); }
-                        else { *dg = g; *dx = gx; }
-                    }
-                }
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // this wavefront's staging traffic is over: the slot may be refilled
-    };
-
-    // Stores a plain epilogue of a full tile issues per wavefront (one per chunk pass, every pass taken): known exactly, so
-    // the first NSTAGE-1 K steps behind the seam -- whose DMAs were issued BEFORE those stores -- wait with the stores
-    // allowed to stay in flight.  (vmcnt is a 6-bit count.)
-    constexpr int S_PLAIN = MT_ * NSPLIT * CPL;
-    static_assert(2 * LPT + S_PLAIN <= 63, "vmcnt immediate");
-    int seam_steps = 0;                // first K steps of this tile whose DMA precedes S_PLAIN in-flight stores of the last epilogue
-    while (bid_c >= 0) {
-        fragment_offsets();
-#pragma clang loop unroll(disable)
-        for (int kc = 0; kc < nkt; ++kc) {
-            // retire step `consumed` only: the steps issued after it stay in flight across the barrier
-            const int ahead = issued - consumed - 1;      // wave-uniform
-            // (the choice between the two counts lives INSIDE one asm statement: as separate statements behind a C++ branch
-            // the same logic costs the 256-wide geometries 12-50 spilled registers -- another block structure for the
-            // scheduler -- and a spilled register is what the asynchronous ticket cannot afford)
-            const int behind_seam = __builtin_amdgcn_readfirstlane(seam_steps > kc ? 1 : 0);
-            if (ahead >= 2)
-                asm volatile("s_cmp_eq_u32 %0, 0\n\ts_cbranch_scc1 1f\n\ts_waitcnt vmcnt(%2)\n\ts_branch 2f\n"
-                             "1:\n\ts_waitcnt vmcnt(%1)\n2:" ::"s"(behind_seam), "n"(2 * LPT), "n"(2 * LPT + S_PLAIN) : "memory", "scc");
-            else if (ahead == 1)
-                asm volatile("s_cmp_eq_u32 %0, 0\n\ts_cbranch_scc1 1f\n\ts_waitcnt vmcnt(%2)\n\ts_branch 2f\n"
-                             "1:\n\ts_waitcnt vmcnt(%1)\n2:" ::"s"(behind_seam), "n"(LPT), "n"(LPT + S_PLAIN) : "memory", "scc");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();          // everyone's part of this step landed; the previous step is fully consumed
-            if (CAN_PERSIST && mb_pending) {       // the ticket drawn two steps ago names the tile after bid_i
-                if (mb_wait == 0) {
-                    if (wave == 0 && lane == 0) {
-                        const int pos = xwg + (int)tk;
-                        const int nb = pos < xcount ? xbase + pos : -1;
-                        asm volatile("ds_write_b32 %0, %1 ; saicv mailbox" :: "v"(mbox_addr), "v"(nb) : "memory");
-                    }
-                    mb_pending = false;
-                } else {
-                    --mb_wait;
-                }
-            }
-            issue_next();                          // refill the slot the previous step just vacated
-            compute(st_c);
-            st_c = (st_c + 1 == NSTAGE) ? 0 : st_c + 1;
-            ++consumed;
-        }
-        // ---- tile seam: the slot of the last K step is free once every wavefront has read its fragments; it is not
-        // refilled before the barrier of the NEXT tile's first step, which every wavefront reaches after its epilogue
-        const int st_last = st_c == 0 ? NSTAGE - 1 : st_c - 1;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        {
-            // exact store count: plain path, no statistics traffic, the tile entirely inside the output (every lane of
-            // every chunk pass stores, so every store instruction is issued)
-            const int tm = bid_c / p.tiles_n, tn = bid_c - tm * p.tiles_n;
-            // (bias loads of the epilogue are waited for by the compiler before the stores are issued: more operations behind
-            // the DMAs than counted, never fewer)
-            const bool exact = !FUSEDK && !do_stats && (tm + 1) * BM_T <= Mc && (tn + 1) * BN_T <= p.Nn;
-            int ex = __builtin_amdgcn_readfirstlane(exact ? NSTAGE - 1 : 0);
-            asm volatile("" : "+s"(ex));       // opaque: keeps the optimiser from specialising the K loop per epilogue path
-            epilogue(bid_c, smem + st_last * STAGE + wave * SLOT_SHARE);
-            seam_steps = ex;
-        }
-#pragma unroll
-        for (int ni = 0; ni < NT_; ++ni)
-#pragma unroll
-            for (int mi = 0; mi < MT_; ++mi) acc[ni][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // the DMA side switched tiles NSTAGE-1 steps ago (host: nkt > NSTAGE in persistent launches), or the stream ended
-        bid_c = persistent ? bid_i : -1;
-    }
-    // ---- persistent launches leave their ticket counters zeroed: the last workgroup to leave resets them
-    if (persistent && wave == 0 && lane == 0) {
-        unsigned int* const done = p.tickets + 32;
-        const unsigned int total = gridDim.x * gridDim.y;
-        if (atomicAdd(done, 1u) == total - 1u) {
-            for (int i = 0; i < 33; ++i) __hip_atomic_store(p.tickets + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------ NT, one tile per workgroup
-// The r02 kernel, kept for every launch that is NOT persistent (at most one round of resident workgroups, short K loops,
-// stride > 1 data-gradient classes, fp32 parity mode, fp32 outputs): its workgroup-wide epilogue (whole tile staged in LDS,
-// statistics over all rows of the tile, eight independent row chunks per thread in flight) is the faster one when nothing
-// follows the tile in the same workgroup, and it writes ONE partial-statistics row per tile row.
+// The tiled kernel of every igemm_nt launch the streaming kernels of pwstream.hip do not take.  One tile per workgroup; its
+// workgroup-wide epilogue (whole tile staged in LDS, statistics over all rows of the tile, eight independent row chunks per
+// thread in flight) writes ONE partial-statistics row per tile row.
 // Main loop = LDS-DMA ring: `buffer_load ... lds` writes global chunks straight into a 4-stage
 // LDS ring (no staging registers, no ds_write), three K tiles are in flight across the single
 // raw s_barrier of each tile, and the wait is a COUNTED s_waitcnt vmcnt(N) that only retires the
@@ -956,7 +210,7 @@ __global__ __launch_bounds__(64 * WM_ * WN_, (BM_T == 256 && BN_T == 128 && !OUT
     constexpr int WMR = BM_T / WM_;              // rows of the output tile owned by one wavefront
     constexpr int WN = BN_T / WN_;
     typedef NtMma<T> MM;
-    constexpr int FR = MM::FR;                   // rows of a fragment (both operands): 32 (bf16, 32x32x16) or 16 (fp32, 16x16x4)
+    constexpr int FR = MM::FR;                   // rows of a fragment (both operands): 16 (bf16 16x16x32, fp32 16x16x4)
     constexpr int NG = MM::NV / 4;               // groups of four consecutive output columns per lane and accumulator tile
     constexpr int KSUB = MM::KSUB;
     constexpr int NT_ = WN / FR;
@@ -1009,8 +263,7 @@ __global__ __launch_bounds__(64 * WM_ * WN_, (BM_T == 256 && BN_T == 128 && !OUT
         Kc = Rc * Sc * p.C;
         nblk = ((Mc + BM_T - 1) / BM_T) * p.tiles_n;
     }
-    // ---- tile loop: one tile per workgroup by default (the hardware dispatcher balances the load); with
-    // SAICV_NT_PERSIST=1 the grid is one resident round of workgroups, each walking tiles tix, tix + grid, ...
+    // ---- tile loop: the host launches one workgroup per tile (the hardware dispatcher balances the load), so the body runs once.
     // Spreading the workgroups' start times over a tile period -- so that epilogue write bursts and MFMA loops of
     // different CUs interleave -- was measured and bought nothing: the ramp costs what the steady state gains.
     for (int tix = blockIdx.x; tix < nblk; tix += gridDim.x) {
@@ -2270,72 +1523,23 @@ void allow_lds(K k, size_t smem) {
     hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
 }
 
-// Ticket counters of persistent launches: a ring of 64 sets (64 dwords each) per device, zero whenever no kernel is using
-// them (the last workgroup of a launch to leave resets its set).  Successive launches take successive sets, so two launches
-// overlapping on different streams do not share one; a captured launch keeps the set it was captured with.
-unsigned int* nt_ticket_set() {
-    static unsigned int* base[16] = {nullptr};
-    static unsigned int seq[16] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-    if (!base[dev]) {
-        void* q = nullptr;
-        if (hipMalloc(&q, 64 * 64 * sizeof(unsigned int)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        if (hipMemset(q, 0, 64 * 64 * sizeof(unsigned int)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(q); return nullptr; }
-        base[dev] = static_cast<unsigned int*>(q);
-    }
-    return base[dev] + (size_t)(seq[dev]++ % 64u) * 64;
-}
-
-// ---- launches.  Streaming kernel: persistent launches only (bf16 in and out); everything else: one tile per workgroup.
-template <int BM_T, int BN_T, int WM_, int WN_, int MODE>
-int launch_nt_stream(NTParams& p, hipStream_t st) {
-    constexpr size_t smem = nt_stages(BM_T, BN_T) * (size_t)(BM_T * 64 + BN_T * 64) + 16;      // DMA ring + ticket mailbox
-    static_assert(nt_can_persist(2, false, BM_T, BN_T, WM_ * WN_), "geometry without a persistent instantiation");
-    p.tickets = nt_ticket_set();
-    SAICV_REQUIRE(p.tickets != nullptr, "igemm_nt: no device memory for the ticket counters");
-    p.grid_x = 256 * nt_blocks_per_cu(BM_T, BN_T);
-    const bool plain = p.R == 1 && p.S == 1 && p.pad == 0 && (MODE == 0 || p.stride == 1);
-    // the plain-epilogue kernel: no fused operand, rows of whole 16-byte chunks at a 16-byte aligned pitch
-    const bool fusedk = p.act_mode != 0 || p.addend != nullptr || p.row_scale != nullptr || p.bs_y != nullptr ||
-                        ((p.ldo * 2) & 15) != 0 || (p.Nn & 7) != 0;
-    dim3 grid(p.grid_x, 1), block(64 * WM_ * WN_);
-#define NT_STREAM_LAUNCH(PL, FK)                                                                   \
-    {                                                                                              \
-        auto k = igemm_nt_kernel<bf16_t, BM_T, BN_T, WM_, WN_, MODE, false, PL, FK>;               \
-        static bool once = (allow_lds(k, 160 * 1024), true);                                       \
-        (void)once;                                                                                \
-        hipLaunchKernelGGL(k, grid, block, smem, st, p);                                           \
-    }
-    if (plain && fusedk) NT_STREAM_LAUNCH(true, true)
-    else if (plain) NT_STREAM_LAUNCH(true, false)
-    else if (fusedk) NT_STREAM_LAUNCH(false, true)
-    else NT_STREAM_LAUNCH(false, false)
-#undef NT_STREAM_LAUNCH
-    return saicv::check_launch("igemm_nt (persistent)");
-}
-
+// ---- launches: one workgroup per tile.  The instantiated forms: fp32 data writes fp32 only; the 256 x 256 tile writes bf16 only
+// (an fp32 output tile would need ~264 KiB of epilogue LDS; pick_tile() never gives it one); 128-byte K slices for pointwise bf16
+// products on the 256-row tiles.
 template <typename T, int BM_T, int BN_T, int WM_, int WN_, int MODE, bool OUT_F32, bool PLAIN, int KC = 4>
-void launch_nt1_inst(const NTParams& p, size_t smem, hipStream_t st) {
+int launch_nt1_inst(const NTParams& p, size_t smem, hipStream_t st) {
     auto k = igemm_nt1_kernel<T, BM_T, BN_T, WM_, WN_, MODE, OUT_F32, PLAIN, KC>;
     static bool once = (allow_lds(k, 160 * 1024), true);
     (void)once;
-    // SAICV_NT1_ROUNDS=r (tuning aid, default 0 = one tile per workgroup): at most r resident rounds of workgroups, each walking the
-    // tiles tix, tix + grid, ... -- the launch-invariant part of the set-up (kernel arguments, divisions: 1.1-2.5 us of a 9-13 us
-    // ResNet-50 tile, profiles/r05_nt_timeline.md) is then paid once per workgroup instead of once per tile
-    int gx = p.nblk;
-    static const int rounds = getenv("SAICV_NT1_ROUNDS") ? atoi(getenv("SAICV_NT1_ROUNDS")) : 0;
-    if (rounds > 0) {
-        const int per_cu = KC == 8 ? 1 : (int)(160 * 1024 / (smem + 1024)) < 1 ? 1 : (int)(160 * 1024 / (smem + 1024));
-        const int cap = 256 * (per_cu > 4 ? 4 : per_cu) * rounds;
-        if (gx > cap) gx = cap;
-    }
-    dim3 grid(gx, (MODE == 1 && p.stride > 1) ? p.stride * p.stride : 1), block(64 * WM_ * WN_);
+    dim3 grid(p.nblk, (MODE == 1 && p.stride > 1) ? p.stride * p.stride : 1), block(64 * WM_ * WN_);
     hipLaunchKernelGGL(k, grid, block, smem, st, p);
+    return saicv::check_launch("igemm_nt");
 }
 
 template <typename T, int BM_T, int BN_T, int WM_, int WN_, int MODE>
-int launch_nt1(NTParams& p, bool out_f32, hipStream_t st) {
+int launch_nt1(const NTParams& p, bool out_f32, hipStream_t st) {
+    constexpr bool F32_OUT = !(BM_T == 256 && BN_T == 256);
+    constexpr bool BF16_OUT = sizeof(T) == 2;
     constexpr size_t smem_full = nt_stages(BM_T, BN_T) * (size_t)(BM_T * 64 + BN_T * 64);      // DMA ring
     const size_t epi = BM_T * (size_t)(BN_T * ((out_f32 || sizeof(T) == 4) ? 4 : 2) + 16) +
                        2 * WM_ * BN_T * sizeof(float);      // staged output tile + per-wavefront BN column sums
@@ -2344,43 +1548,44 @@ int launch_nt1(NTParams& p, bool out_f32, hipStream_t st) {
 #ifdef SAICV_NT_TIMELINE
     if (getenv("SAICV_NT_SOLO") && smem < 84 * 1024) smem = 84 * 1024;      // debug build: one workgroup per CU (what a lone K loop sustains)
 #endif
-    p.tickets = nullptr;
-    p.grid_x = p.nblk;
     // pointwise taps without padding: the source pixel of a row never leaves the image
     const bool plain = p.R == 1 && p.S == 1 && p.pad == 0 && (MODE == 0 || p.stride == 1);
-    // 128-byte K slices: chosen by igemm_nt (p.kc8)
-    if constexpr (sizeof(T) == 2 && BM_T == 256) {
+    if constexpr (BF16_OUT && BM_T == 256) {
         if (p.kc8 && plain && !out_f32) {
             constexpr size_t ring = nt_stages_kc8(BM_T, BN_T) * (size_t)(BM_T + BN_T) * 128;
-            launch_nt1_inst<T, BM_T, BN_T, WM_, WN_, MODE, false, true, 8>(p, ring < epi ? epi : ring, st);
-            return saicv::check_launch("igemm_nt");
+            return launch_nt1_inst<T, BM_T, BN_T, WM_, WN_, MODE, false, true, 8>(p, ring < epi ? epi : ring, st);
         }
     }
-    if (out_f32) {
-        if (plain) launch_nt1_inst<T, BM_T, BN_T, WM_, WN_, MODE, true, true>(p, smem, st);
-        else launch_nt1_inst<T, BM_T, BN_T, WM_, WN_, MODE, true, false>(p, smem, st);
-    } else {
-        if (plain) launch_nt1_inst<T, BM_T, BN_T, WM_, WN_, MODE, false, true>(p, smem, st);
-        else launch_nt1_inst<T, BM_T, BN_T, WM_, WN_, MODE, false, false>(p, smem, st);
+    if constexpr (F32_OUT) {
+        if (out_f32) {
+            if (plain) return launch_nt1_inst<T, BM_T, BN_T, WM_, WN_, MODE, true, true>(p, smem, st);
+            return launch_nt1_inst<T, BM_T, BN_T, WM_, WN_, MODE, true, false>(p, smem, st);
+        }
     }
-    return saicv::check_launch("igemm_nt");
+    if constexpr (BF16_OUT) {
+        if (!out_f32) {
+            if (plain) return launch_nt1_inst<T, BM_T, BN_T, WM_, WN_, MODE, false, true>(p, smem, st);
+            return launch_nt1_inst<T, BM_T, BN_T, WM_, WN_, MODE, false, false>(p, smem, st);
+        }
+    }
+    saicv::set_error("igemm_nt: the %d x %d tile has no %s-output form for %s data", BM_T, BN_T, out_f32 ? "fp32" : "bf16",
+                     sizeof(T) == 2 ? "bf16" : "fp32");
+    return -1;
 }
 
-// Tile choice shared by the kernel launch and conv_stat_rows(): relative per-flop speed of each geometry x
+// Tile choice of nt_plan(): relative per-flop speed of each geometry x
 // wave-quantisation efficiency on 256 CUs x useful fraction of the tile.  The speeds are fitted to a sweep of
 // every geometry over the 23 ResNet-50 shapes and the ViT / SAM linear shapes (scripts/gpu_tiles.sh, r01e): two
 // co-resident 256 x 128 workgroups hide each other's epilogue (launch, prologue latency, store drain: ~11 us per
 // 64 K outputs per CU whatever the geometry), which beats one 256 x 256 workgroup until the K loop is long enough
 // (~100 K tiles) for its lower LDS traffic per flop to matter.
-struct NTTile { int bm, bn, wm, blocks_per_cu; float speed; float fixed_us, step_us; };   // tile time = fixed + K tiles x step (fit)
-const NTTile kTiles[5] = {{256, 256, 2, 1, 0.80f, 11.8f, 0.905f}, {256, 128, 4, 2, 1.00f, 9.95f, 0.97f},
-                           {128, 128, 2, 2, 0.60f, 6.1f, 0.60f}, {128, 64, 2, 3, 0.50f, 4.55f, 0.685f},
-                           {256, 128, 2, 2, 0.00f, 9.95f, 0.97f}};      // [4]: 256 x 128 on FOUR wavefronts of 128 x 64 (SAICV_NT_TILE=4)
+struct NTTile { int bm, bn, blocks_per_cu; float speed; };
+const NTTile kTiles[4] = {{256, 256, 1, 0.80f}, {256, 128, 2, 1.00f}, {128, 128, 2, 0.60f}, {128, 64, 3, 0.50f}};
 
 int pick_tile(int M, int Nn, int nkt, bool f32_out_big) {
     if (const char* force = getenv("SAICV_NT_TILE")) {      // tuning aid: force a geometry
         const int t = atoi(force);
-        if (t >= 0 && t < 5 && !(f32_out_big && kTiles[t].bm * kTiles[t].bn * 4 > 150 * 1024)) return t;
+        if (t >= 0 && t < 4 && !(f32_out_big && kTiles[t].bm * kTiles[t].bn * 4 > 150 * 1024)) return t;
     }
     int best = 2;
     float best_score = -1.f;
@@ -2401,42 +1606,79 @@ int pick_tile(int M, int Nn, int nkt, bool f32_out_big) {
     return best;
 }
 
-// What a launch will do, as a pure function of the problem (conv_stat_rows() must size the statistics buffer before the
-// launch): geometry, and whether the launch is PERSISTENT -- the streaming kernel, one partial-statistics row per (tile row,
-// wavefront row) -- or one tile per workgroup (one row per tile row).  Persistent: bf16 in and out, a geometry with a
-// persistent instantiation, more tiles than resident workgroups, a K loop longer than the DMA ring, not a stride > 1 data
-// gradient (its parity classes have unequal, possibly empty K loops).  SAICV_NT_PERSIST=0 turns it off.
-struct NTPlan { int tile; bool persist; };
-NTPlan nt_plan(int dtype, int mode, int stride, int M_tile, int Nn, int nkt, bool f32o) {
-    NTPlan pl;
-    pl.tile = pick_tile(M_tile, Nn, nkt, f32o);
-    const NTTile& g = kTiles[pl.tile];
-    // OFF by default (r03 measurement, profiles/r03_streaming_kernel.md): the streaming kernel is 3-14 % ahead of the one-tile
-    // kernel on isolated ViT-B GEMMs with wide outputs, level elsewhere -- and BEHIND inside the models on the same box
-    // (ResNet-50 23.8 vs 22.6 ms per step with every eligible layer persistent, ViT-B 44.9 vs 44.3 ms with the rule below):
-    // a ViT-B launch is ~7 tiles per workgroup, a ResNet-50 launch 1-3 rounds -- the ramp of a staggered start costs what
-    // the interleaved store bursts gain.  SAICV_NT_PERSIST=1 turns the rule below on, with SAICV_NT_TILE every eligible launch.
-    const char* pe = getenv("SAICV_NT_PERSIST");                       // (read per call: a tuning sweep flips it in-process)
-    const int persist_env = pe ? atoi(pe) : 0;
-    const long nblk = (long)((Nn + g.bn - 1) / g.bn) * ((M_tile + g.bm - 1) / g.bm);
-    const int nwaves = g.wm * (pl.tile == 0 ? 4 : 2);
-    const bool can = persist_env && dtype == SAICV_DTYPE_BF16 && !f32o && !(mode == 1 && stride > 1);
-    pl.persist = can && getenv("SAICV_NT_TILE") != nullptr && nt_can_persist(2, false, g.bm, g.bn, nwaves) &&
-                 nblk > 256L * nt_blocks_per_cu(g.bm, g.bn) && nkt > nt_stages(g.bm, g.bn);
-    if (pl.tile == 4 && !pl.persist) pl.tile = 1;      // the four-wavefront 256 x 128 geometry exists in the streaming kernel only
-    if (!getenv("SAICV_NT_TILE") && can && !pl.persist) {
-        // Where the streaming kernel (256 x 256 tiles, staggered start) measured ahead of the tile picker's one-tile choice
-        // (profiles/r03_nt_sweep_*.jsonl: M = 50 432 rows, +9..14 % on N = 2304 / 3072 outputs with K = 768 and on long
-        // reductions; level or behind on N = 768 and on every ResNet-50 shape, whose launches are one to three rounds):
-        // at least four rounds of tiles per CU, nearly full last round, and wide outputs with a short K loop or a long K loop.
-        const long t0 = (long)((Nn + 255) / 256) * ((M_tile + 255) / 256);
-        const float rounds = (float)t0 / 256.f;
-        const float quant = rounds / (float)(long)(rounds + 0.999999f);
-        if (t0 >= 4 * 256 && quant >= 0.85f && nkt > nt_stages(256, 256) && ((Nn >= 2048 && nkt <= 32) || nkt >= 64)) {
-            pl.tile = 0;
-            pl.persist = true;
+// Everything that decides how igemm_nt runs a product.
+struct NTProblem {
+    int dtype, mode;
+    int H, W, C, OH, OW, R, S, stride, pad;      // gather source, row pixel grid, taps (igemm_nt's arguments)
+    int M, Nn, Kd, ldo;
+    bool out_f32;                                // fp32 output of bf16 data
+    bool bias, stats, addend, row_scale, out2, bn_sums;      // which epilogue operands are present (bn_sums: EpiExtra::bs_*)
+    int act_mode;
+};
+enum NTRoute { NT_TILED, NT_PW_STREAM, NT_PW3_STREAM };
+struct NTPlan {
+    NTRoute route;
+    int tile;           // NT_TILED: kTiles index
+    bool kc8;           // NT_TILED: the 128-byte-K-slice instantiation
+    int blocks;         // NT_PW_STREAM / NT_PW3_STREAM: workgroups
+    int stat_rows;      // rows of partial statistics (forward sums or BatchNorm-backward sums) the launch writes
+};
+
+// How igemm_nt runs a product, as a pure function of the problem and of the tuning switches SAICV_PW_STREAM, SAICV_PW_STREAM3,
+// SAICV_PW_MIN_ROWS, SAICV_NT_KC8 and SAICV_NT_TILE (read per call: tests and sweeps flip them in-process).  The launch and
+// the partial-statistics row queries (conv_stat_rows, conv_bwd_stat_rows) both ask it, so a buffer sized by a query always
+// matches the launch.
+NTPlan nt_plan(const NTProblem& q) {
+    NTPlan pl = {NT_TILED, 0, false, 0, 0};
+    // the weight-resident streaming kernels of pwstream.hip: bf16 in and out, dense rows, a plain epilogue (statistics, or a
+    // data gradient's shortcut addend / BatchNorm-backward sums, never both) -- no tiles, no workgroup barriers, one partial
+    // row per workgroup
+    const bool streamable = q.dtype == SAICV_DTYPE_BF16 && !q.out_f32 && q.stride == 1 && q.ldo == q.Nn && !q.bias && !q.act_mode &&
+                            !q.row_scale && !q.out2 && !(q.stats && (q.addend || q.bn_sums));
+    // small-K x small-N pointwise products over many rows (ResNet stage 1-2 1 x 1 convolutions and their data gradients)
+    if (streamable && q.R == 1 && q.S == 1 && q.pad == 0) {
+        pl.blocks = saicv::pw_stream_blocks(q.dtype, q.M, q.Nn, q.Kd, (q.addend || q.bn_sums) && !q.stats);
+        if (pl.blocks > 0) {
+            pl.route = NT_PW_STREAM;
+            pl.stat_rows = pl.blocks;
+            return pl;
         }
     }
+    // ... and the 3 x 3 / stride 1 / padding 1 convolution 64 -> 64 of the same stage and its data gradient, as the same stream over nine taps
+    if (streamable && q.R == 3 && q.S == 3 && q.pad == 1 && q.C == 64 && q.H == q.OH && q.W == q.OW && q.H >= 1 && q.W >= 1 &&
+        q.M % (q.H * q.W) == 0) {
+        pl.blocks = saicv::pw3_stream_blocks(q.dtype, q.M, q.Nn, q.Kd);
+        if (pl.blocks > 0) {
+            pl.route = NT_PW3_STREAM;
+            pl.stat_rows = pl.blocks;
+            return pl;
+        }
+    }
+    const bool f32o = q.out_f32 || q.dtype == SAICV_DTYPE_F32;
+    int M_tile = q.M;
+    if (q.mode == 1 && q.stride > 1)       // largest parity class
+        M_tile = (q.M / (q.OH * q.OW)) * ((q.OH + q.stride - 1) / q.stride) * ((q.OW + q.stride - 1) / q.stride);
+    const int bk = q.dtype == SAICV_DTYPE_BF16 ? 32 : 16;
+    pl.tile = pick_tile(M_tile, q.Nn, (q.Kd + bk - 1) / bk, f32o);      // K tiles (stride > 1 data-gradient classes run fewer)
+    // 128-byte K slices (igemm_nt1_kernel, KC = 8) on the 256 x 256 tile: one workgroup per CU, so only where the main loop is
+    // long against the exposed prologue / epilogue and the launch fills the CUs several times.  SAICV_NT_KC8: 0 never,
+    // 1 every eligible launch of a 256-row tile, 2 (default) wide pointwise GEMMs without a fused activation, 3 the same with
+    // them -- measured on the ViT-B shapes (profiles/r03_lds_fill_and_kc8.md): +10...13 % for N >= 2048, K = 768; -8 % for
+    // N = K = 768; the GELU-fused launches (two output tensors / one more input in the epilogue) lose 10 % with one workgroup
+    // per CU: ViT-B step 42.57 ms off, 42.95 with them, 42.31 without.
+    const char* ke = getenv("SAICV_NT_KC8");
+    const int kc8_mode = ke ? atoi(ke) : 2;
+    const bool pointwise = q.R == 1 && q.S == 1 && q.pad == 0 && (q.mode == 0 || q.stride == 1);
+    const bool ok = q.dtype == SAICV_DTYPE_BF16 && !f32o && pointwise && kTiles[pl.tile].bm == 256 && q.Kd >= 256;
+    if (ok && kc8_mode == 1) pl.kc8 = true;
+    const bool rule_ok = (kc8_mode == 2 && q.act_mode == 0) || kc8_mode == 3;
+    if (ok && rule_ok && q.Nn >= 2048 && q.Nn % 256 == 0 && q.Kd >= 512 && (long)((M_tile + 255) / 256) * (q.Nn / 256) >= 4 * 256) {
+        pl.kc8 = true;
+        pl.tile = 0;
+    }
+    // one row per tile row, per parity class of a stride > 1 data gradient
+    const int classes = q.mode == 1 && q.stride > 1 ? q.stride * q.stride : 1;
+    pl.stat_rows = ((M_tile + kTiles[pl.tile].bm - 1) / kTiles[pl.tile].bm) * classes;
     return pl;
 }
 
@@ -2475,31 +1717,20 @@ int launch_tn_dma(const TNParams& p, int splits, bool plain, hipStream_t st) {
 
 namespace saicv {
 
-// rows of BN partial statistics written by the forward kernel: one per row of workgroups (per row of wavefronts when the
-// launch is persistent)
-int conv_stat_rows(int M, int Nn, int Kd, int dtype, int form) {
-    if (form) {                                            // the streaming kernels' row per workgroup (csrc/pwstream.hip)
-        const int pw = form == 1 ? pw_stream_blocks(dtype, M, Nn, Kd, false) : pw3_stream_blocks(dtype, M, Nn, Kd);
-        if (pw > 0) return pw;
-    }
-    const int bk = dtype == SAICV_DTYPE_BF16 ? 32 : 16;
-    const NTPlan pl = nt_plan(dtype, 0, 1, M, Nn, (Kd + bk - 1) / bk, dtype == SAICV_DTYPE_F32);
-    const NTTile& g = kTiles[pl.tile];
-    return ((M + g.bm - 1) / g.bm) * (pl.persist ? g.wm : 1);
+// rows of BatchNorm partial statistics saicv_conv2d_fwd writes with stat_sum (the output in the data type, no bias)
+int conv_stat_rows(const saicv_conv_desc* d) {
+    const NTProblem q = {d->dtype, 0, d->H, d->W, d->C, d->OH, d->OW, d->R, d->S, d->stride, d->pad,
+                         d->N * d->OH * d->OW, d->K, d->R * d->S * d->C, d->K,
+                         /*out_f32=*/false, /*bias=*/false, /*stats=*/true, false, false, false, false, 0};
+    return nt_plan(q).stat_rows;
 }
 
-// partial rows the data gradient writes with EpiExtra::bs_*: (rows of tiles of the largest parity class) x classes
-int conv_bwd_stat_rows(int M, int OH, int OW, int Nn, int Kd, int stride, int dtype, int form) {
-    if (form && stride == 1) {
-        const int pw = form == 1 ? pw_stream_blocks(dtype, M, Nn, Kd, true) : pw3_stream_blocks(dtype, M, Nn, Kd);
-        if (pw > 0) return pw;
-    }
-    const int bk = dtype == SAICV_DTYPE_BF16 ? 32 : 16;
-    int M_tile = M;
-    if (stride > 1) M_tile = (M / (OH * OW)) * ((OH + stride - 1) / stride) * ((OW + stride - 1) / stride);
-    const NTPlan pl = nt_plan(dtype, 1, stride, M_tile, Nn, (Kd + bk - 1) / bk, dtype == SAICV_DTYPE_F32);
-    const NTTile& g = kTiles[pl.tile];
-    return ((M_tile + g.bm - 1) / g.bm) * stride * stride * (pl.persist ? g.wm : 1);
+// rows of BatchNorm-backward partial sums saicv_conv2d_dgrad_fused writes with bn_y (with or without the shortcut addend)
+int conv_bwd_stat_rows(const saicv_conv_desc* d) {
+    const NTProblem q = {d->dtype, 1, d->OH, d->OW, d->K, d->H, d->W, d->R, d->S, d->stride, d->pad,
+                         d->N * d->H * d->W, d->C, d->R * d->S * d->K, d->C,
+                         /*out_f32=*/false, false, false, false, false, false, /*bn_sums=*/true, 0};
+    return nt_plan(q).stat_rows;
 }
 
 // r05, measured and NOT kept: cutting a badly quantised linear GEMM (ViT-B's 768-wide outputs: 1 182 tiles of 256 x 128 on 512 slots
@@ -2533,7 +1764,6 @@ int igemm_nt(int dtype, int mode, const void* src, const void* wgt, void* out, c
     p.bs_gx = ex ? ex->bs_gx : nullptr;
     p.bs_rows = 0;
     p.stat_atomic_rows = ex ? ex->stat_atomic_rows : 0;
-    p.tickets = nullptr;
 #ifdef SAICV_NT_TIMELINE
     p.timeline = g_nt_timeline;
 #endif
@@ -2560,23 +1790,18 @@ int igemm_nt(int dtype, int mode, const void* src, const void* wgt, void* out, c
         SAICV_REQUIRE((ldo * osz) % 16 == 0, "igemm_nt: fused residual needs a 16-byte aligned leading dimension");
         SAICV_REQUIRE(p.rows_per_scale >= 1, "igemm_nt: rows_per_scale must be >= 1");
     }
-    // Small-K x small-N pointwise products over many rows (ResNet stage 1-2 1 x 1 convolutions and their data gradients): the
-    // weight-resident streaming kernel of pwstream.hip -- no tiles, no workgroup barriers, one partial row per workgroup.
-    if (dtype == SAICV_DTYPE_BF16 && !out_f32 && R == 1 && S == 1 && pad == 0 && stride == 1 && ldo == Nn && !bias && !p.act_mode &&
-        !p.row_scale && !p.out2 && !(stat_sum && (p.addend || p.bs_y))) {
-        static const long min_mb = getenv("SAICV_NT_STREAM_MIN_MB") ? atol(getenv("SAICV_NT_STREAM_MIN_MB")) : 0;
-        const int so = (size_t)M * Nn * 2 >= (size_t)min_mb * 1024 * 1024 ? 1 : 0;
-        const int rc = pw_stream(M, Nn, Kd, src, wgt, out, stat_sum, stat_sq, p.stat_atomic_rows, ex, so, st);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
-    // ... and the 3 x 3 / stride 1 / padding 1 convolution 64 -> 64 of the same stage and its data gradient, as the same stream over nine taps
-    if (dtype == SAICV_DTYPE_BF16 && !out_f32 && R == 3 && S == 3 && pad == 1 && stride == 1 && C == 64 && Nn == 64 && Kd == 576 && ldo == Nn &&
-        H == OH && W == OW && !bias && !p.act_mode && !p.row_scale && !p.out2 && !(stat_sum && (p.addend || p.bs_y))) {
-        static const long min_mb3 = getenv("SAICV_NT_STREAM_MIN_MB") ? atol(getenv("SAICV_NT_STREAM_MIN_MB")) : 0;
-        const int so = (size_t)M * Nn * 2 >= (size_t)min_mb3 * 1024 * 1024 ? 1 : 0;
-        const int rc = pw3_stream(mode, M, H, W, src, wgt, out, stat_sum, stat_sq, p.stat_atomic_rows, ex, so, st);
-        if (rc != 0) return rc < 0 ? rc : 0;
-    }
+    const NTProblem q = {dtype, mode, H, W, C, OH, OW, R, S, stride, pad, M, Nn, Kd, ldo, out_f32 != 0,
+                         bias != nullptr, stat_sum != nullptr, p.addend != nullptr, p.row_scale != nullptr, p.out2 != nullptr,
+                         p.bs_y != nullptr, p.act_mode};
+    const NTPlan pl = nt_plan(q);
+    const bool f32o = out_f32 != 0 || dtype == SAICV_DTYPE_F32;
+    // streaming output stores from SAICV_NT_STREAM_MIN_MB MiB of output on (0: always; a huge value: never)
+    static const long min_mb = getenv("SAICV_NT_STREAM_MIN_MB") ? atol(getenv("SAICV_NT_STREAM_MIN_MB")) : 0;
+    const int stream_out = (size_t)M * Nn * (f32o ? 4 : 2) >= (size_t)min_mb * 1024 * 1024 ? 1 : 0;
+    if (pl.route == NT_PW_STREAM)
+        return pw_stream(M, Nn, Kd, src, wgt, out, stat_sum, stat_sq, p.stat_atomic_rows, ex, stream_out, pl.blocks, st);
+    if (pl.route == NT_PW3_STREAM)
+        return pw3_stream(mode, M, H, W, src, wgt, out, stat_sum, stat_sq, p.stat_atomic_rows, ex, stream_out, pl.blocks, st);
     p.H = H; p.W = W; p.C = C; p.OH = OH; p.OW = OW; p.R = R; p.S = S; p.stride = stride; p.pad = pad;
     p.M = M; p.Nn = Nn; p.Kd = Kd; p.ldo = ldo;
     const size_t esz = dtype == SAICV_DTYPE_BF16 ? 2 : 4;
@@ -2588,95 +1813,19 @@ int igemm_nt(int dtype, int mode, const void* src, const void* wgt, void* out, c
     p.wgt_bytes = (uint32_t)wgt_bytes;
     p.fd_ohw = make_fastdiv((uint32_t)(OH * OW));
     p.fd_ow = make_fastdiv((uint32_t)OW);
-    const bool f32o = out_f32 != 0 || dtype == SAICV_DTYPE_F32;
-    int M_tile = M;
-    if (mode == 1 && stride > 1) {
-        const int nimg = M / (OH * OW);
-        M_tile = nimg * ((OH + stride - 1) / stride) * ((OW + stride - 1) / stride);   // largest parity class
-    }
-    const int nkt_host = (Kd + 4 * epc - 1) / (4 * epc);      // K tiles (stride > 1 data-gradient classes run fewer)
-    NTPlan pl = nt_plan(dtype, mode, stride, M_tile, Nn, nkt_host, f32o);
-    {
-        // SAICV_NT_PERSIST=2: the streaming kernel only for launches with a plain epilogue (bias at most) -- the fused modes run
-        // in its rolled per-wavefront loops.  Statistics launches keep the plan conv_stat_rows() sized their buffers with.
-        const char* pe = getenv("SAICV_NT_PERSIST");
-        const bool fused = p.act_mode || p.addend || p.row_scale || p.out2 || p.addend_gate || p.bs_y;
-        if (pl.persist && pe && atoi(pe) == 2 && fused && !stat_sum) {
-            pl.persist = false;
-            pl.tile = pick_tile(M_tile, Nn, nkt_host, f32o);
-            if (pl.tile == 4) pl.tile = 1;
-        }
-    }
-    int t = pl.tile;
-    // 128-byte K slices (igemm_nt1_kernel, KC = 8) on the 256 x 256 tile: one workgroup per CU, so only where the main loop is
-    // long against the exposed prologue / epilogue and the launch fills the CUs several times.  SAICV_NT_KC8: 0 never,
-    // 1 every eligible launch of a 256-row tile, 2 (default) wide pointwise GEMMs without a fused activation, 3 the same with
-    // them -- measured on the ViT-B shapes (profiles/r03_lds_fill_and_kc8.md): +10...13 % for N >= 2048, K = 768; -8 % for
-    // N = K = 768; the GELU-fused launches (two output tensors / one more input in the epilogue) lose 10 % with one workgroup
-    // per CU: ViT-B step 42.57 ms off, 42.95 with them, 42.31 without.
-    const char* ke = getenv("SAICV_NT_KC8");             // read per call
-    const int kc8_mode = ke ? atoi(ke) : 2;
-    {
-        // streaming output stores from SAICV_NT_STREAM_MIN_MB MiB of output on (0: always; a huge value: never)
-        static const long min_mb = getenv("SAICV_NT_STREAM_MIN_MB") ? atol(getenv("SAICV_NT_STREAM_MIN_MB")) : 0;
-        const size_t out_bytes = (size_t)M * Nn * ((out_f32 || dtype == SAICV_DTYPE_F32) ? 4 : 2);
-        p.stream_out = out_bytes >= (size_t)min_mb * 1024 * 1024 ? 1 : 0;
-    }
-    p.kc8 = 0;
-    {
-        const bool pointwise = R == 1 && S == 1 && pad == 0 && (mode == 0 || stride == 1);
-        const bool ok = dtype == SAICV_DTYPE_BF16 && !f32o && pointwise && !pl.persist && kTiles[t].bm == 256 && Kd >= 256;
-        if (ok && kc8_mode == 1) p.kc8 = 1;
-        const bool rule_ok = (kc8_mode == 2 && p.act_mode == 0) || kc8_mode == 3;
-        if (ok && rule_ok && Nn >= 2048 && Nn % 256 == 0 && Kd >= 512 && (long)((M_tile + 255) / 256) * (Nn / 256) >= 4 * 256) {
-            p.kc8 = 1;
-            t = 0;
-        }
-    }
+    p.stream_out = stream_out;
+    p.kc8 = pl.kc8 ? 1 : 0;
     // (r03's staged-range main loop for 3 x 3 / stride 1 convolutions -- one contiguous input range per channel slice instead of nine
     // gathered taps, LDS-fill traffic / 2.3 -- measured level with the gather on every ResNet-50 layer (profiles/r03_lds_fill_and_kc8.md
     // section 7) and was removed in r05.)
-    const NTTile& g = kTiles[t];
+    const NTTile& g = kTiles[pl.tile];
+    const int classes = mode == 1 && stride > 1 ? stride * stride : 1;
+    p.bs_rows = pl.stat_rows / classes;
     p.tiles_n = (Nn + g.bn - 1) / g.bn;
-    p.nblk = p.tiles_n * ((M_tile + g.bm - 1) / g.bm);
-    p.bs_rows = (M_tile + g.bm - 1) / g.bm;
-    p.stagger_phases = 0;
-    p.stagger_sleeps = 0;
-    if (pl.persist) {
-        // start phases: SAICV_NT_STAGGER = number of phase groups (default 8; 0 or 1 = none), spread over one tile period
-        // (estimated from the fitted step time of the geometry; SAICV_NT_STAGGER_US overrides the period)
-        const char* sp = getenv("SAICV_NT_STAGGER");
-        const char* su = getenv("SAICV_NT_STAGGER_US");
-        const int phases = sp ? atoi(sp) : 8;
-        if (phases > 1) {
-            const float period_us = su ? (float)atof(su) : (float)nkt_host * g.step_us * (g.blocks_per_cu > 1 ? 1.f : 1.f);
-            p.stagger_phases = phases;
-            p.stagger_sleeps = (int)(period_us / (float)phases / 0.5f + 0.5f);
-        }
-        if (mode == 0) {
-            switch (t) {
-                case 0: return launch_nt_stream<256, 256, 2, 4, 0>(p, st);
-                case 2: return launch_nt_stream<128, 128, 2, 2, 0>(p, st);
-                case 3: return launch_nt_stream<128, 64, 2, 2, 0>(p, st);
-                default: return launch_nt_stream<256, 128, 2, 2, 0>(p, st);
-            }
-        } else {
-            switch (t) {
-                case 0: return launch_nt_stream<256, 256, 2, 4, 1>(p, st);
-                case 2: return launch_nt_stream<128, 128, 2, 2, 1>(p, st);
-                case 3: return launch_nt_stream<128, 64, 2, 2, 1>(p, st);
-                default: return launch_nt_stream<256, 128, 2, 2, 1>(p, st);
-            }
-        }
-    }
-// -DSAICV_NT_T0_WN=2: the 256 x 256 tile on FOUR wavefronts of 128 x 128 (with -DSAICV_NT_MFMA32: the probe's cheapest form per flop)
-#ifndef SAICV_NT_T0_WN
-#define SAICV_NT_T0_WN 4
-#endif
-#define NT_T0_WN SAICV_NT_T0_WN
+    p.nblk = p.tiles_n * p.bs_rows;
 #define NT_DISPATCH(TT, MODE_)                                                              \
-    switch (t) {                                                                            \
-        case 0: return launch_nt1<TT, 256, 256, 2, NT_T0_WN, MODE_>(p, f32o, st);           \
+    switch (pl.tile) {                                                                      \
+        case 0: return launch_nt1<TT, 256, 256, 2, 4, MODE_>(p, f32o, st);                  \
         case 1: return launch_nt1<TT, 256, 128, 4, 2, MODE_>(p, f32o, st);                  \
         case 2: return launch_nt1<TT, 128, 128, 2, 2, MODE_>(p, f32o, st);                  \
         default: return launch_nt1<TT, 128, 64, 2, 2, MODE_>(p, f32o, st);                  \

@@ -430,7 +430,7 @@ int pw_stream_blocks(int dtype, int M, int Nn, int Kd, bool fused_dgrad) {
     const char* er = getenv("SAICV_PW_MIN_ROWS");
     const int on = es ? atoi(es) : 1;
     const int min_rows = er ? atoi(er) : 65536;
-    if (!on || dtype != SAICV_DTYPE_BF16 || M < min_rows) return 0;
+    if (!on || dtype != SAICV_DTYPE_BF16 || M < min_rows || (size_t)M * Kd * 2 >= 0xfffffff0ull) return 0;
     for (const PWShape& s : kShapes) {
         if (s.kd != Kd || s.nd != Nn) continue;
         // K = 256: only the data gradient with fused operands (143 us against 159 tiled); forward + statistics and the plain data
@@ -446,13 +446,10 @@ int pw_stream_blocks(int dtype, int M, int Nn, int Kd, bool fused_dgrad) {
     return 0;
 }
 
-// -> 1 launched, 0 not eligible (the caller takes the tiled kernel), < 0 error
+// `blocks` workgroups, as pw_stream_blocks() gave them to igemm_nt's plan.  -> 0, < 0 error
 int pw_stream(int M, int Nn, int Kd, const void* src, const void* wgt, void* out, float* stat_sum, float* stat_sq,
-              int stat_atomic_rows, const EpiExtra* ex, int stream_out, hipStream_t st) {
+              int stat_atomic_rows, const EpiExtra* ex, int stream_out, int blocks, hipStream_t st) {
     const bool extras = ex && (ex->addend || ex->bs_y);
-    const int blocks = pw_stream_blocks(SAICV_DTYPE_BF16, M, Nn, Kd, extras && !stat_sum);
-    if (blocks == 0) return 0;
-    if (stat_sum && extras) return 0;
     PWParams p = {};
     p.src = (const bf16_t*)src; p.wgt = (const bf16_t*)wgt; p.out = (bf16_t*)out;
     p.stat_sum = stat_sum; p.stat_sq = stat_sq;
@@ -462,9 +459,7 @@ int pw_stream(int M, int Nn, int Kd, const void* src, const void* wgt, void* out
         p.bs_y = (const bf16_t*)ex->bs_y; p.bs_mask = ex->bs_mask; p.bs_mean = ex->bs_mean; p.bs_invstd = ex->bs_invstd;
         p.bs_g = ex->bs_g; p.bs_gx = ex->bs_gx;
     }
-    const size_t src_bytes = (size_t)M * Kd * 2;
-    if (src_bytes >= 0xfffffff0ull) return 0;
-    p.src_bytes = (uint32_t)src_bytes;
+    p.src_bytes = (uint32_t)((size_t)M * Kd * 2);
     p.M = M;
     p.mtiles = (M + 15) / 16;
     p.stream_out = stream_out;
@@ -473,8 +468,7 @@ int pw_stream(int M, int Nn, int Kd, const void* src, const void* wgt, void* out
     if (Kd == KD && Nn == ND) {                                                    \
         constexpr int NW = NS > 4 ? NS : 4;                                        \
         p.units = blocks * (NW / NS);                                              \
-        const int rc = launch<KD, ND, NS>(p, blocks, stats, extras, st);           \
-        return rc ? rc : 1;                                                        \
+        return launch<KD, ND, NS>(p, blocks, stats, extras, st);                   \
     }
     PW_CASE(64, 64, 1)
     PW_CASE(64, 256, 4)
@@ -483,7 +477,8 @@ int pw_stream(int M, int Nn, int Kd, const void* src, const void* wgt, void* out
     PW_CASE(128, 512, 8)
     PW_CASE(128, 256, 4)
 #undef PW_CASE
-    return 0;
+    set_error("pw_stream: no form for K = %d, N = %d", Kd, Nn);
+    return -1;
 }
 
 // The 3 x 3 / stride 1 / padding 1 form (64 -> 64 channels): workgroups (= rows of partial statistics), 0 if the tiled kernel keeps it.
@@ -492,20 +487,18 @@ int pw3_stream_blocks(int dtype, int M, int Nn, int Kd) {
     const char* er = getenv("SAICV_PW_MIN_ROWS");
     const int on = es ? atoi(es) : 1;
     const int min_rows = er ? atoi(er) : 65536;
-    if (!on || dtype != SAICV_DTYPE_BF16 || M < min_rows || Nn != 64 || Kd != 576) return 0;
+    if (!on || dtype != SAICV_DTYPE_BF16 || M < min_rows || Nn != 64 || Kd != 576 || (size_t)M * 64 * 2 >= 0xffffff00ull - 256) return 0;
     const int mtiles = (M + 15) / 16;
     const int want = (mtiles + 7) / 8;
     return want < 256 ? want : 256;
 }
 
 // src [N][H][W][64] (M = N * H * W rows), wgt [64][(r, s, c)]; mode 0: out(y, x) = sum wgt(r, s) . src(y + r - 1, x + s - 1), mode 1 (the
-// data gradient over the packed transposed weights): src(y + 1 - r, x + 1 - s).  -> 1 launched, 0 not eligible, < 0 error
+// data gradient over the packed transposed weights): src(y + 1 - r, x + 1 - s).  `blocks` workgroups, as pw3_stream_blocks() gave them
+// to igemm_nt's plan.  -> 0, < 0 error
 int pw3_stream(int mode, int M, int H, int W, const void* src, const void* wgt, void* out, float* stat_sum, float* stat_sq,
-               int stat_atomic_rows, const EpiExtra* ex, int stream_out, hipStream_t st) {
-    const int blocks = pw3_stream_blocks(SAICV_DTYPE_BF16, M, 64, 576);
-    if (blocks == 0) return 0;
+               int stat_atomic_rows, const EpiExtra* ex, int stream_out, int blocks, hipStream_t st) {
     const bool extras = ex && (ex->addend || ex->bs_y);
-    if (stat_sum && extras) return 0;
     PWParams p = {};
     p.src = (const bf16_t*)src; p.wgt = (const bf16_t*)wgt; p.out = (bf16_t*)out;
     p.stat_sum = stat_sum; p.stat_sq = stat_sq;
@@ -515,9 +508,7 @@ int pw3_stream(int mode, int M, int H, int W, const void* src, const void* wgt, 
         p.bs_y = (const bf16_t*)ex->bs_y; p.bs_mask = ex->bs_mask; p.bs_mean = ex->bs_mean; p.bs_invstd = ex->bs_invstd;
         p.bs_g = ex->bs_g; p.bs_gx = ex->bs_gx;
     }
-    const size_t src_bytes = (size_t)M * 64 * 2;
-    if (src_bytes >= 0xffffff00ull - 256 || H < 1 || W < 1 || M % (H * W) != 0) return 0;
-    p.src_bytes = (uint32_t)src_bytes;
+    p.src_bytes = (uint32_t)((size_t)M * 64 * 2);
     p.M = M;
     p.mtiles = (M + 15) / 16;
     p.units = blocks * 8;
@@ -525,8 +516,7 @@ int pw3_stream(int mode, int M, int H, int W, const void* src, const void* wgt, 
     p.H = H; p.W = W;
     p.tap_sign = mode == 0 ? 1 : -1;
     p.stream_out = stream_out;
-    const int rc = launch_taps9(p, blocks, stat_sum != nullptr, extras, st);
-    return rc ? rc : 1;
+    return launch_taps9(p, blocks, stat_sum != nullptr, extras, st);
 }
 
 }  // namespace saicv

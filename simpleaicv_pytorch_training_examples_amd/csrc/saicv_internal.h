@@ -2,14 +2,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+struct saicv_conv_desc;      // include/saicv_hip.h
+
 namespace saicv {
 
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
 
-// igemm.hip
-// form: 1 = the product reads whole consecutive rows of its source (pointwise, stride 1, no padding), 2 = 3 x 3 / stride 1 / padding 1
-int conv_stat_rows(int M, int Nn, int Kd, int dtype, int form = 0);
+// igemm.hip: rows of partial statistics saicv_conv2d_fwd writes with statistics (the launch's own plan)
+int conv_stat_rows(const saicv_conv_desc* d);
 // optional epilogue extras: out = addend + row_scale[m / rows_per_scale] * (acc + bias)
 struct EpiExtra {
     const void* addend = nullptr;      // same dtype / layout as out
@@ -27,8 +28,8 @@ struct EpiExtra {
     float* bs_gx = nullptr;
     int stat_atomic_rows = 0;              // > 0: statistics added atomically into this many rows of a zeroed buffer
 };
-// partial rows the data gradient (mode 1; M rows on the OH x OW pixel grid) writes with bs_*
-int conv_bwd_stat_rows(int M, int OH, int OW, int Nn, int Kd, int stride, int dtype, int form = 0);
+// ... and the BatchNorm-backward partial rows saicv_conv2d_dgrad_fused writes with bn_y
+int conv_bwd_stat_rows(const saicv_conv_desc* d);
 int igemm_nt(int dtype, int mode, const void* src, const void* wgt, void* out, const float* bias,
              float* stat_sum, float* stat_sq, int H, int W, int C, int OH, int OW, int R, int S,
              int stride, int pad, int M, int Nn, int Kd, int ldo, int out_f32, hipStream_t st,
@@ -37,13 +38,14 @@ int igemm_tn(int dtype, const void* dy, const void* src, float* dw, int H, int W
              int OW, int R, int S, int stride, int pad, int M, int Cout, int Kd, hipStream_t st,
              float* dbias = nullptr);
 
-// pwstream.hip: weight-resident streaming kernel for small pointwise products; blocks = rows of partial statistics (0: not eligible)
+// pwstream.hip: weight-resident streaming kernel for small pointwise products; blocks = rows of partial statistics (0: not eligible).
+// igemm_nt launches them with the block count of its plan.
 int pw_stream_blocks(int dtype, int M, int Nn, int Kd, bool fused_dgrad);
 int pw_stream(int M, int Nn, int Kd, const void* src, const void* wgt, void* out, float* stat_sum, float* stat_sq,
-              int stat_atomic_rows, const EpiExtra* ex, int stream_out, hipStream_t st);
+              int stat_atomic_rows, const EpiExtra* ex, int stream_out, int blocks, hipStream_t st);
 int pw3_stream_blocks(int dtype, int M, int Nn, int Kd);
 int pw3_stream(int mode, int M, int H, int W, const void* src, const void* wgt, void* out, float* stat_sum, float* stat_sq,
-               int stat_atomic_rows, const EpiExtra* ex, int stream_out, hipStream_t st);
+               int stat_atomic_rows, const EpiExtra* ex, int stream_out, int blocks, hipStream_t st);
 
 // sam.hip
 int window_partition(int dtype, const void* x, void* out, int B, int H, int W, int C, int ws, hipStream_t st);

@@ -1,10 +1,4 @@
-"""Generated-code check of the persistent implicit-GEMM kernels (no GPU needed: hipcc cross-compiles gfx950 assembly).
-
-csrc/igemm.hip draws a workgroup's next tile with a returning atomic that is hidden from the compiler inside inline asm
-(the compiler would wait vmcnt(0) right behind it -- the whole LDS-DMA ring plus an L2 round trip per tile).  The price is
-that nothing tells the compiler the destination register is still in flight; scripts/check_ticket_regs.py verifies in the
-assembly of EVERY persistent-capable instantiation that the register is written by the draws only, read by the mailbox
-write only, never copied or spilled, and that such kernels use no scratch memory at all."""
+"""Generated-code checks of the HIP kernels (no GPU needed: hipcc cross-compiles gfx950 assembly)."""
 import os
 import sys
 
@@ -12,15 +6,6 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'scripts'))
-
-
-@pytest.mark.timeout(900)
-def test_ticket_register_of_persistent_kernels_is_untouched_between_draw_and_use():
-    import check_ticket_regs as C
-    report = C.check(C.assembly())
-    assert len(report) == 32                                  # 4 geometries x fwd / dgrad x pointwise / gather x plain / fused epilogue
-    for name, reg, draws, boxes in report:
-        assert draws >= 2 and boxes == 1, (name, reg, draws, boxes)
 
 
 @pytest.mark.timeout(900)
@@ -46,7 +31,7 @@ def test_streaming_kernels_of_the_late_additions_keep_their_registers(source, tm
 
 
 @pytest.mark.timeout(1200)
-def test_asm_fragment_reads_are_not_touched_before_their_counted_wait():
+def test_asm_fragment_reads_of_each_kernel_are_not_touched_before_their_counted_wait():
     """the `ds_read_b128` fragment reads of csrc/igemm.hip and csrc/pwstream.hip are inline asm with `=v` outputs the
     compiler treats as valid at once, released by hand-counted `s_waitcnt lgkmcnt(N)` asm statements.  scripts/check_fragment_regs.py
     replays the LGKM counter over the generated assembly of every kernel: no instruction reads or writes a fragment register while
@@ -55,11 +40,11 @@ def test_asm_fragment_reads_are_not_touched_before_their_counted_wait():
     a wait count raised by two, and a move inserted behind a read, must both be reported."""
     import re
     import check_fragment_regs as F
-    import check_ticket_regs as C
     pw = F.assembly('pwstream.hip')
-    reports = F.check(pw) + F.check(C.assembly())
+    reports = F.check(pw) + F.check(F.assembly('igemm.hip'))
     assert len([r for r in reports if 'pw_stream_kernel' in r[0]]) == 3           # the nine-tap forms: plain, + statistics, + data-gradient extras
-    assert len(reports) >= 60, len(reports)
+    # + the 32 bf16 forms of igemm_nt1_kernel and the 10 of igemm_tn_dma_kernel
+    assert len(reports) == 3 + 32 + 10, len(reports)
     for name, n_reads, n_waits, scratch, bad in reports:
         assert n_reads >= 1 and n_waits >= 1 and scratch == 0 and not bad, (name, n_reads, n_waits, scratch, bad[:3])
     # mutation 1: the first three counted waits release two reads too few
@@ -85,3 +70,40 @@ def test_asm_fragment_reads_are_not_touched_before_their_counted_wait():
             lines.insert(i + 2, '\tv_mov_b32_e32 v200, v' + re.search(r'v\[(\d+):', l).group(1))
             break
     assert sum(len(r[4]) for r in F.check('\n'.join(lines))) == 1
+
+
+def _igemm_kernels_expected():
+    """The kernels csrc/igemm.hip instantiates (mangled, after the anonymous-namespace prefix): every form a launch can reach, no other."""
+    nt1 = 'igemm_nt1_kernelI{}Li{}ELi{}ELi{}ELi{}ELi{}ELb{:d}ELb{:d}ELi{}EEEvNS_8NTParamsE'
+    tiles = [(256, 256, 2, 4), (256, 128, 4, 2), (128, 128, 2, 2), (128, 64, 2, 2)]
+    names = set()
+    for mode in (0, 1):
+        for plain in (False, True):
+            for tile in tiles:
+                wide = tile[:2] == (256, 256)             # bf16 output only: an fp32 output tile would not fit the epilogue LDS
+                names.add(nt1.format('DF16b', *tile, mode, False, plain, 4))
+                if not wide:
+                    names.add(nt1.format('DF16b', *tile, mode, True, plain, 4))
+                    names.add(nt1.format('f', *tile, mode, True, plain, 4))      # fp32 data always writes fp32
+        for tile in tiles[:2]:                            # 128-byte K slices: pointwise bf16, 256-row tiles
+            names.add(nt1.format('DF16b', *tile, mode, False, True, 8))
+    tn = [(64, 64, 2, 2), (64, 128, 2, 2), (128, 64, 2, 2), (128, 128, 2, 2), (256, 256, 2, 4)]
+    for g in tn:
+        for t in ('DF16b', 'f'):
+            names.add('igemm_tn_kernelI{}Li{}ELi{}ELi{}ELi{}EEEvNS_8TNParamsE'.format(t, *g))
+        for plain in (False, True):
+            names.add('igemm_tn_dma_kernelILi{}ELi{}ELi{}ELi{}ELb{:d}EEEvNS_8TNParamsE'.format(*g, plain))
+    return names
+
+
+@pytest.mark.timeout(1200)
+def test_igemm_instantiates_exactly_the_launchable_kernels():
+    """44 igemm_nt1_kernel forms (no fp32 data with a bf16 output, no fp32 output on the 256 x 256 tile), 10 igemm_tn_kernel, 10
+    igemm_tn_dma_kernel: a form the dispatch cannot reach is not compiled."""
+    import re
+    import check_fragment_regs as F
+    found = re.findall(r'^\s*\.amdhsa_kernel _ZN12_GLOBAL__N_1\d+(\S+)$', F.assembly('igemm.hip'), re.M)
+    expected = _igemm_kernels_expected()
+    assert len(expected) == 64 and len([n for n in expected if n.startswith('igemm_nt1_kernel')]) == 44
+    assert len(found) == len(set(found))
+    assert set(found) == expected, (sorted(set(found) - expected), sorted(expected - set(found)))
