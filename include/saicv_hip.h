@@ -170,6 +170,45 @@ typedef struct saicv_dgrad_fuse {
 int saicv_conv2d_dgrad_stat_rows(const saicv_conv_desc* d);
 int saicv_conv2d_dgrad_fused(const saicv_conv_desc* d, const void* dy, const void* wd, const saicv_dgrad_fuse* f, void* dx,
                              void* stream);
+/* ---- launch plan query ------------------------------------------------------------------
+ * What the convolution / linear entry points above decide before they launch, as a host-side function of the problem
+ * alone: no tensors, no stream, nothing reaches the GPU.  It asks the same plan functions the launches ask and reads the
+ * same per-call tuning switches (SAICV_NT_TILE, SAICV_NT_KC8, SAICV_PW_STREAM, SAICV_PW_STREAM3, SAICV_PW_MIN_ROWS,
+ * SAICV_TN_SLOTS_PCT, SAICV_TN_DMA), so a test can assert which kernel form a shape takes and enumerate the forms a
+ * list of shapes reaches.  The flag fields say which optional operands the call would pass (0 / 1). */
+#define SAICV_PLAN_CONV_FWD 0      /* saicv_conv2d_fwd, _fwd_stats           (conv; out_f32, bias, stats)                      */
+#define SAICV_PLAN_CONV_DGRAD 1    /* saicv_conv2d_dgrad, _dgrad_add, _fused (conv; addend, bn_sums)                           */
+#define SAICV_PLAN_CONV_WGRAD 2    /* saicv_conv2d_wgrad, _wgrad_bias        (conv)                                            */
+#define SAICV_PLAN_LINEAR_FWD 3    /* saicv_linear_fwd, _gelu_fwd, _gelu_fwd_aux (dtype, M, K, N; out_f32, bias, addend, row_scale, act_mode 0 / 1 / 3) */
+#define SAICV_PLAN_LINEAR_DGRAD 4  /* saicv_linear_dgrad, _dgrad_gelu, _dgrad_mul (dtype, M, K, N; addend, act_mode 0 / 2 / 4) */
+#define SAICV_PLAN_LINEAR_WGRAD 5  /* saicv_linear_wgrad                     (dtype, M, K, N)                                  */
+typedef struct saicv_plan_query {
+    int op;                 /* SAICV_PLAN_*                            */
+    saicv_conv_desc conv;   /* convolution ops                         */
+    int dtype, M, K, N;     /* linear ops, as the entry points take them */
+    int out_f32, bias, stats, addend, row_scale, bn_sums, act_mode;
+} saicv_plan_query;
+#define SAICV_ROUTE_TILED 0        /* igemm_nt1_kernel, one workgroup per tile          */
+#define SAICV_ROUTE_PW_STREAM 1    /* pw_stream_kernel, pointwise                       */
+#define SAICV_ROUTE_PW3_STREAM 2   /* pw_stream_kernel, the nine-tap 64 -> 64 form      */
+#define SAICV_ROUTE_TN 3           /* igemm_tn_dma_kernel / igemm_tn_kernel (weight gradients) */
+typedef struct saicv_plan {
+    int route;              /* SAICV_ROUTE_*                                                                              */
+    int tile;               /* tiled: 0..3 = 256x256, 256x128, 128x128, 128x64; weight gradient: 0..4 = 64x64, 64x128, 128x64, 128x128, 256x256 */
+    int bm, bn;             /* the tile's rows x columns (weight gradient: output channels x reduction columns)            */
+    int kc8;                /* tiled: 128-byte K slices                                                                   */
+    int plain;              /* pointwise form: no tap walker (tiled); row m of x is row m of the product (weight gradient, DMA kernel) */
+    int out_f32;            /* the output is fp32                                                                         */
+    int dma;                /* weight gradient: the LDS-DMA kernel (1) or the register-staged one (0)                     */
+    int blocks;             /* workgroups of the launch                                                                   */
+    int stat_rows;          /* rows of partial statistics the launch writes (= saicv_conv2d_stat_rows / _dgrad_stat_rows)  */
+    int splits;             /* weight gradient: workgroups sharing one tile's pixel reduction ...                         */
+    int rt_per, total_rt;   /* ... each taking rt_per of the total_rt reduction steps ...                                  */
+    int rows_per_step;      /* ... of this many rows; (splits - 1) * rt_per < total_rt: no split is empty                  */
+} saicv_plan;
+/* -> 0, or -1 where the entry point itself would refuse the problem (saicv_last_error_string says why) */
+int saicv_igemm_plan(const saicv_plan_query* q, saicv_plan* plan);
+
 /* out[r][:] = x[r][:] * scale[r / rows_per_scale] */
 int saicv_row_scale(int dtype, const void* x, const float* scale, void* out, size_t rows, int row_len,
                     int rows_per_scale, void* stream);

@@ -51,6 +51,23 @@ class DgradFuse(Structure):
 _PF = POINTER(DgradFuse)
 
 
+class PlanQuery(Structure):
+    """saicv_plan_query (include/saicv_hip.h)"""
+    _fields_ = [('op', c_int), ('conv', ConvDesc), ('dtype', c_int), ('M', c_int), ('K', c_int), ('N', c_int),
+                ('out_f32', c_int), ('bias', c_int), ('stats', c_int), ('addend', c_int), ('row_scale', c_int),
+                ('bn_sums', c_int), ('act_mode', c_int)]
+
+
+class Plan(Structure):
+    """saicv_plan (include/saicv_hip.h)"""
+    _fields_ = [(n, c_int) for n in ('route', 'tile', 'bm', 'bn', 'kc8', 'plain', 'out_f32', 'dma', 'blocks', 'stat_rows',
+                                     'splits', 'rt_per', 'total_rt', 'rows_per_step')]
+
+
+PLAN_CONV_FWD, PLAN_CONV_DGRAD, PLAN_CONV_WGRAD, PLAN_LINEAR_FWD, PLAN_LINEAR_DGRAD, PLAN_LINEAR_WGRAD = range(6)
+ROUTE_TILED, ROUTE_PW_STREAM, ROUTE_PW3_STREAM, ROUTE_TN = range(4)
+
+
 class PackDesc(Structure):
     """saicv_pack_desc (include/saicv_hip.h)"""
     _fields_ = [('w', c_void_p), ('sO', c_long), ('sI', c_long), ('sR', c_long), ('sS', c_long),
@@ -95,6 +112,7 @@ SIGNATURES = {
     'saicv_conv2d_dgrad_add': (c_int, [_PD, _P, _P, _P, _P, _P]),
     'saicv_conv2d_dgrad_stat_rows': (c_int, [_PD]),
     'saicv_conv2d_dgrad_fused': (c_int, [_PD, _P, _P, _PF, _P, _P]),
+    'saicv_igemm_plan': (c_int, [POINTER(PlanQuery), POINTER(Plan)]),
     'saicv_conv2d_fwd_stats': (c_int, [_PD, _P, _P, _P, _P, _P, c_int, _P]),
     'saicv_bn_act_fwd_stats': (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_double, _P, _P, _P, _P, c_double, c_double, _P, _P, _P,
                                        c_size_t, c_int, c_int, _P, _P]),

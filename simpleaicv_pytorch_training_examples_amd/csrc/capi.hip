@@ -264,6 +264,16 @@ int saicv_conv2d_dgrad_fused(const saicv_conv_desc* d, const void* dy, const voi
                     d->R, d->S, d->stride, d->pad, M, d->C, d->R * d->S * d->K, d->C, 0, S(stream),
                     (f->addend || f->bn_y) ? &ex : nullptr);
 }
+int saicv_igemm_plan(const saicv_plan_query* q, saicv_plan* plan) {
+    if (!q || !plan) { set_error("saicv_igemm_plan: null argument"); return -1; }
+    SAICV_REQUIRE(q->op >= SAICV_PLAN_CONV_FWD && q->op <= SAICV_PLAN_LINEAR_WGRAD, "saicv_igemm_plan: bad op %d", q->op);
+    if (q->op <= SAICV_PLAN_CONV_WGRAD) {
+        if (check_desc(&q->conv, "saicv_igemm_plan")) return -1;
+    } else {
+        SAICV_REQUIRE(q->dtype == SAICV_BF16 || q->dtype == SAICV_F32, "saicv_igemm_plan: bad dtype %d", q->dtype);
+    }
+    return igemm_plan(q, plan);
+}
 int saicv_row_scale(int dtype, const void* x, const float* scale, void* out, size_t rows, int row_len,
                     int rows_per_scale, void* stream) {
     return row_scale(dtype, x, scale, out, rows, row_len, rows_per_scale, S(stream));

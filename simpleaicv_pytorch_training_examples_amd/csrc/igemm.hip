@@ -1524,8 +1524,8 @@ void allow_lds(K k, size_t smem) {
 }
 
 // ---- launches: one workgroup per tile.  The instantiated forms: fp32 data writes fp32 only; the 256 x 256 tile writes bf16 only
-// (an fp32 output tile would need ~264 KiB of epilogue LDS; pick_tile() never gives it one); 128-byte K slices for pointwise bf16
-// products on the 256-row tiles.
+// (an fp32 output tile would need ~264 KiB of epilogue LDS; pick_tile() never gives it one); bf16 data writes fp32 in the forward
+// mode only; 128-byte K slices for pointwise bf16 products on the 256-row tiles.
 template <typename T, int BM_T, int BN_T, int WM_, int WN_, int MODE, bool OUT_F32, bool PLAIN, int KC = 4>
 int launch_nt1_inst(const NTParams& p, size_t smem, hipStream_t st) {
     auto k = igemm_nt1_kernel<T, BM_T, BN_T, WM_, WN_, MODE, OUT_F32, PLAIN, KC>;
@@ -1537,8 +1537,9 @@ int launch_nt1_inst(const NTParams& p, size_t smem, hipStream_t st) {
 }
 
 template <typename T, int BM_T, int BN_T, int WM_, int WN_, int MODE>
-int launch_nt1(const NTParams& p, bool out_f32, hipStream_t st) {
-    constexpr bool F32_OUT = !(BM_T == 256 && BN_T == 256);
+int launch_nt1(const NTParams& p, bool out_f32, bool plain, hipStream_t st) {
+    // fp32 output of bf16 data: forward only (logits, fp32 residual streams) -- no public entry point asks a data gradient for it
+    constexpr bool F32_OUT = !(BM_T == 256 && BN_T == 256) && (sizeof(T) == 4 || MODE == 0);
     constexpr bool BF16_OUT = sizeof(T) == 2;
     constexpr size_t smem_full = nt_stages(BM_T, BN_T) * (size_t)(BM_T * 64 + BN_T * 64);      // DMA ring
     const size_t epi = BM_T * (size_t)(BN_T * ((out_f32 || sizeof(T) == 4) ? 4 : 2) + 16) +
@@ -1548,8 +1549,6 @@ int launch_nt1(const NTParams& p, bool out_f32, hipStream_t st) {
 #ifdef SAICV_NT_TIMELINE
     if (getenv("SAICV_NT_SOLO") && smem < 84 * 1024) smem = 84 * 1024;      // debug build: one workgroup per CU (what a lone K loop sustains)
 #endif
-    // pointwise taps without padding: the source pixel of a row never leaves the image
-    const bool plain = p.R == 1 && p.S == 1 && p.pad == 0 && (MODE == 0 || p.stride == 1);
     if constexpr (BF16_OUT && BM_T == 256) {
         if (p.kc8 && plain && !out_f32) {
             constexpr size_t ring = nt_stages_kc8(BM_T, BN_T) * (size_t)(BM_T + BN_T) * 128;
@@ -1620,7 +1619,9 @@ struct NTPlan {
     NTRoute route;
     int tile;           // NT_TILED: kTiles index
     bool kc8;           // NT_TILED: the 128-byte-K-slice instantiation
-    int blocks;         // NT_PW_STREAM / NT_PW3_STREAM: workgroups
+    bool plain;         // NT_TILED: pointwise taps without padding (the source pixel of a row never leaves the image): no tap walker
+    bool f32o;          // NT_TILED: the output is fp32 (fp32 data, or bf16 data with out_f32)
+    int blocks;         // workgroups (NT_TILED: one per tile, all parity classes of a stride > 1 data gradient)
     int stat_rows;      // rows of partial statistics (forward sums or BatchNorm-backward sums) the launch writes
 };
 
@@ -1629,7 +1630,7 @@ struct NTPlan {
 // the partial-statistics row queries (conv_stat_rows, conv_bwd_stat_rows) both ask it, so a buffer sized by a query always
 // matches the launch.
 NTPlan nt_plan(const NTProblem& q) {
-    NTPlan pl = {NT_TILED, 0, false, 0, 0};
+    NTPlan pl = {NT_TILED, 0, false, false, false, 0, 0};
     // the weight-resident streaming kernels of pwstream.hip: bf16 in and out, dense rows, a plain epilogue (statistics, or a
     // data gradient's shortcut addend / BatchNorm-backward sums, never both) -- no tiles, no workgroup barriers, one partial
     // row per workgroup
@@ -1669,6 +1670,8 @@ NTPlan nt_plan(const NTProblem& q) {
     const char* ke = getenv("SAICV_NT_KC8");
     const int kc8_mode = ke ? atoi(ke) : 2;
     const bool pointwise = q.R == 1 && q.S == 1 && q.pad == 0 && (q.mode == 0 || q.stride == 1);
+    pl.plain = pointwise;
+    pl.f32o = f32o;
     const bool ok = q.dtype == SAICV_DTYPE_BF16 && !f32o && pointwise && kTiles[pl.tile].bm == 256 && q.Kd >= 256;
     if (ok && kc8_mode == 1) pl.kc8 = true;
     const bool rule_ok = (kc8_mode == 2 && q.act_mode == 0) || kc8_mode == 3;
@@ -1679,7 +1682,91 @@ NTPlan nt_plan(const NTProblem& q) {
     // one row per tile row, per parity class of a stride > 1 data gradient
     const int classes = q.mode == 1 && q.stride > 1 ? q.stride * q.stride : 1;
     pl.stat_rows = ((M_tile + kTiles[pl.tile].bm - 1) / kTiles[pl.tile].bm) * classes;
+    pl.blocks = pl.stat_rows * ((q.Nn + kTiles[pl.tile].bn - 1) / kTiles[pl.tile].bn);
     return pl;
+}
+
+// operands the tiled kernel addresses through 32-bit buffer offsets
+bool nt_operands_fit(const NTProblem& q) {
+    const size_t esz = q.dtype == SAICV_DTYPE_BF16 ? 2 : 4;
+    const size_t src_bytes = (size_t)(q.M / (q.OH * q.OW)) * q.H * q.W * q.C * esz;
+    const size_t wgt_bytes = (size_t)q.Nn * q.Kd * esz;
+    return src_bytes < 0xfffffff0ull && wgt_bytes < 0xfffffff0ull;
+}
+
+// Everything that decides how igemm_tn runs a weight gradient.
+struct TNProblem {
+    int dtype;
+    int H, W, C, OH, OW, R, S, stride, pad;
+    int M, Cout, Kd;
+};
+struct TNPlan {
+    bool big;           // the 256 x 256 tile
+    int ba, bb;         // tile: ba output channels x bb reduction columns (r, s, c)
+    int tiles_a, tiles_b;
+    int BR;             // rows of a reduction step the splits are counted in
+    int total_rt;       // reduction steps of the whole product
+    int rt_per;         // ... of one split
+    int splits;
+    bool dma;           // igemm_tn_dma_kernel (bf16) / the register-staged igemm_tn_kernel
+    bool plain;         // igemm_tn_dma_kernel: 1 x 1 / stride 1 / no padding (row m of the source is row m of the GEMM)
+};
+
+// How igemm_tn runs a product, as a pure function of the problem, of the switches SAICV_TN_BIG (read once), SAICV_TN_SLOTS_PCT and
+// SAICV_TN_DMA (read per call) and of whether the process holds a multi-rank communicator.  The launch and the plan query both ask it.
+TNPlan tn_plan(const TNProblem& q) {
+    TNPlan pl;
+    const int epc = q.dtype == SAICV_DTYPE_BF16 ? 8 : 4;
+    const int M = q.M, Cout = q.Cout, Kd = q.Kd;
+    const int BR = 8 * epc;
+    pl.BR = BR;
+    // 256 x 256 tiles (8 wavefronts of 128 x 64) halve both the HBM/L2 traffic and the LDS fragment reads per
+    // MFMA of the 128 x 128 geometry; used when both output dimensions fill them
+    // ... when both output dimensions fill them and every workgroup keeps >= 48 reduction steps (below that the
+    // 256 KiB of fp32 atomics per workgroup outweigh the gain: the small-M ResNet stages stay on 128 x 128)
+    static const int force_big = getenv("SAICV_TN_BIG") ? atoi(getenv("SAICV_TN_BIG")) : -1;
+    const int big_tiles = ((Cout + 255) / 256) * ((Kd + 255) / 256);
+    const int big_steps = ((M + BR - 1) / BR) / (256 / big_tiles > 0 ? 256 / big_tiles : 1);
+    const bool big = force_big >= 0 ? (force_big != 0 && Cout >= 128 && Kd >= 128)
+                                    : (Cout % 256 == 0 && Kd >= 256 && (Kd % 256 == 0 || Kd >= 1024) && big_steps >= 48);
+    pl.big = big;
+    const int ba = big ? 256 : Cout <= 64 ? 64 : 128;
+    const int bb = big ? 256 : Kd <= 64 ? 64 : 128;
+    pl.ba = ba; pl.bb = bb;
+    pl.tiles_a = (Cout + ba - 1) / ba;
+    pl.tiles_b = (Kd + bb - 1) / bb;
+    const int tiles = pl.tiles_a * pl.tiles_b;
+    // split the pixel reduction so that ~4 workgroups per CU are in flight
+    const int total_rt = (M + BR - 1) / BR;
+    // 128-wide tiles: 2 workgroups per CU are resident (73 KiB LDS each); 256-wide: one (139 KiB)
+    // rounded DOWN: one full round of resident workgroups beats a second, nearly empty one
+    // The split count is sized for ALL resident slots when this GPU runs nothing else, and for 85 % of them once the process has
+    // created an RCCL communicator over more than one rank (g_saicv_comm_world, comm.hip): the one-round design has no slack -- under
+    // data-parallel training RCCL's all-reduce kernels hold CU slots (and LDS) during backward, and every workgroup that cannot
+    // start with the others costs this kernel a whole second round.  Measured on one GPU (r05, same box, twice each): 100 against
+    // 85 is ViT-B 40.02 -> 39.52 ms (weight gradients 10.0 -> 9.4 ms), ResNet-50 21.00 -> 20.95 ms; 70 is ResNet-50 21.60 ms.
+    // SAICV_TN_SLOTS_PCT overrides (read per call; e.g. 85 for a torch.distributed process group without the native communicator).
+    const char* slots_env = getenv("SAICV_TN_SLOTS_PCT");
+    const int slots_pct = slots_env ? atoi(slots_env) : (g_saicv_comm_world > 1 ? 85 : 100);
+    int splits = ((big ? 256 : 512) * slots_pct / 100) / tiles;
+    if (splits > total_rt) splits = total_rt;
+    if (splits < 1) splits = 1;
+    int rt_per = (total_rt + splits - 1) / splits;
+    splits = (total_rt + rt_per - 1) / rt_per;
+    pl.total_rt = total_rt; pl.rt_per = rt_per; pl.splits = splits;
+    // bf16: the LDS-DMA ring kernel (32-row steps; SAICV_TN_DMA=0 selects the register-staged kernel for A/B runs)
+    const char* de = getenv("SAICV_TN_DMA");             // read per call
+    const int use_dma = de ? atoi(de) : 1;
+    pl.dma = use_dma && q.dtype == SAICV_DTYPE_BF16;
+    pl.plain = q.R == 1 && q.S == 1 && q.stride == 1 && q.pad == 0 && q.H == q.OH && q.W == q.OW;
+    return pl;
+}
+
+bool tn_operands_fit(const TNProblem& q) {
+    const size_t esz = q.dtype == SAICV_DTYPE_BF16 ? 2 : 4;
+    const size_t dy_bytes = (size_t)q.M * q.Cout * esz;
+    const size_t src_bytes = (size_t)(q.M / (q.OH * q.OW)) * q.H * q.W * q.C * esz;
+    return dy_bytes < 0xfffffff0ull && src_bytes < 0xfffffff0ull;
 }
 
 template <typename T, int BA, int BB, int NWA = 2, int NWB = 2>
@@ -1805,12 +1892,9 @@ int igemm_nt(int dtype, int mode, const void* src, const void* wgt, void* out, c
     p.H = H; p.W = W; p.C = C; p.OH = OH; p.OW = OW; p.R = R; p.S = S; p.stride = stride; p.pad = pad;
     p.M = M; p.Nn = Nn; p.Kd = Kd; p.ldo = ldo;
     const size_t esz = dtype == SAICV_DTYPE_BF16 ? 2 : 4;
-    const size_t src_bytes = (size_t)(M / (OH * OW)) * H * W * C * esz;
-    const size_t wgt_bytes = (size_t)Nn * Kd * esz;
-    SAICV_REQUIRE(src_bytes < 0xfffffff0ull && wgt_bytes < 0xfffffff0ull,
-                  "igemm_nt: operand larger than 4 GiB (buffer addressing)");
-    p.src_bytes = (uint32_t)src_bytes;
-    p.wgt_bytes = (uint32_t)wgt_bytes;
+    SAICV_REQUIRE(nt_operands_fit(q), "igemm_nt: operand larger than 4 GiB (buffer addressing)");
+    p.src_bytes = (uint32_t)((size_t)(M / (OH * OW)) * H * W * C * esz);
+    p.wgt_bytes = (uint32_t)((size_t)Nn * Kd * esz);
     p.fd_ohw = make_fastdiv((uint32_t)(OH * OW));
     p.fd_ow = make_fastdiv((uint32_t)OW);
     p.stream_out = stream_out;
@@ -1825,10 +1909,10 @@ int igemm_nt(int dtype, int mode, const void* src, const void* wgt, void* out, c
     p.nblk = p.tiles_n * p.bs_rows;
 #define NT_DISPATCH(TT, MODE_)                                                              \
     switch (pl.tile) {                                                                      \
-        case 0: return launch_nt1<TT, 256, 256, 2, 4, MODE_>(p, f32o, st);                  \
-        case 1: return launch_nt1<TT, 256, 128, 4, 2, MODE_>(p, f32o, st);                  \
-        case 2: return launch_nt1<TT, 128, 128, 2, 2, MODE_>(p, f32o, st);                  \
-        default: return launch_nt1<TT, 128, 64, 2, 2, MODE_>(p, f32o, st);                  \
+        case 0: return launch_nt1<TT, 256, 256, 2, 4, MODE_>(p, f32o, pl.plain, st);                  \
+        case 1: return launch_nt1<TT, 256, 128, 4, 2, MODE_>(p, f32o, pl.plain, st);                  \
+        case 2: return launch_nt1<TT, 128, 128, 2, 2, MODE_>(p, f32o, pl.plain, st);                  \
+        default: return launch_nt1<TT, 128, 64, 2, 2, MODE_>(p, f32o, pl.plain, st);                  \
     }
     if (dtype == SAICV_DTYPE_BF16) {
         if (mode == 0) { NT_DISPATCH(bf16_t, 0) } else { NT_DISPATCH(bf16_t, 1) }
@@ -1838,7 +1922,7 @@ int igemm_nt(int dtype, int mode, const void* src, const void* wgt, void* out, c
 #undef NT_DISPATCH
 }
 
-static int igemm_tn_launch(int dtype, TNParams& p, int splits, bool big, int ba, int bb, int BR, hipStream_t st);
+static int igemm_tn_launch(int dtype, TNParams& p, const TNPlan& pl, hipStream_t st);
 
 int igemm_tn(int dtype, const void* dy, const void* src, float* dw, int H, int W, int C, int OH,
              int OW, int R, int S, int stride, int pad, int M, int Cout, int Kd, hipStream_t st, float* dbias) {
@@ -1848,77 +1932,45 @@ int igemm_tn(int dtype, const void* dy, const void* src, float* dw, int H, int W
     TNParams p;
     p.dy = dy; p.src = src; p.dw = dw; p.dbias = dbias; p.H = H; p.W = W; p.C = C; p.OH = OH; p.OW = OW;
     p.R = R; p.S = S; p.stride = stride; p.pad = pad; p.M = M; p.Cout = Cout; p.Kd = Kd;
+    const TNProblem q = {dtype, H, W, C, OH, OW, R, S, stride, pad, M, Cout, Kd};
     const size_t esz = dtype == SAICV_DTYPE_BF16 ? 2 : 4;
-    const size_t dy_bytes = (size_t)M * Cout * esz;
-    const size_t src_bytes = (size_t)(M / (OH * OW)) * H * W * C * esz;
-    SAICV_REQUIRE(dy_bytes < 0xfffffff0ull && src_bytes < 0xfffffff0ull,
-                  "igemm_tn: operand larger than 4 GiB (buffer addressing)");
-    p.dy_bytes = (uint32_t)dy_bytes;
-    p.src_bytes = (uint32_t)src_bytes;
+    SAICV_REQUIRE(tn_operands_fit(q), "igemm_tn: operand larger than 4 GiB (buffer addressing)");
+    p.dy_bytes = (uint32_t)((size_t)M * Cout * esz);
+    p.src_bytes = (uint32_t)((size_t)(M / (OH * OW)) * H * W * C * esz);
     p.fd_ohw = make_fastdiv((uint32_t)(OH * OW));
     p.fd_ow = make_fastdiv((uint32_t)OW);
-    const int BR = 8 * epc;
-    // 256 x 256 tiles (8 wavefronts of 128 x 64) halve both the HBM/L2 traffic and the LDS fragment reads per
-    // MFMA of the 128 x 128 geometry; used when both output dimensions fill them
-    // ... when both output dimensions fill them and every workgroup keeps >= 48 reduction steps (below that the
-    // 256 KiB of fp32 atomics per workgroup outweigh the gain: the small-M ResNet stages stay on 128 x 128)
-    static const int force_big = getenv("SAICV_TN_BIG") ? atoi(getenv("SAICV_TN_BIG")) : -1;
-    const int big_tiles = ((Cout + 255) / 256) * ((Kd + 255) / 256);
-    const int big_steps = ((M + BR - 1) / BR) / (256 / big_tiles > 0 ? 256 / big_tiles : 1);
-    const bool big = force_big >= 0 ? (force_big != 0 && Cout >= 128 && Kd >= 128)
-                                    : (Cout % 256 == 0 && Kd >= 256 && (Kd % 256 == 0 || Kd >= 1024) && big_steps >= 48);
-    const int ba = big ? 256 : Cout <= 64 ? 64 : 128;
-    const int bb = big ? 256 : Kd <= 64 ? 64 : 128;
-    p.tiles_a = (Cout + ba - 1) / ba;
-    p.tiles_b = (Kd + bb - 1) / bb;
-    const int tiles = p.tiles_a * p.tiles_b;
-    // split the pixel reduction so that ~4 workgroups per CU are in flight
-    const int total_rt = (M + BR - 1) / BR;
-    // 128-wide tiles: 2 workgroups per CU are resident (73 KiB LDS each); 256-wide: one (139 KiB)
-    // rounded DOWN: one full round of resident workgroups beats a second, nearly empty one
-    // The split count is sized for ALL resident slots when this GPU runs nothing else, and for 85 % of them once the process has
-    // created an RCCL communicator over more than one rank (g_saicv_comm_world, comm.hip): the one-round design has no slack -- under
-    // data-parallel training RCCL's all-reduce kernels hold CU slots (and LDS) during backward, and every workgroup that cannot
-    // start with the others costs this kernel a whole second round.  Measured on one GPU (r05, same box, twice each): 100 against
-    // 85 is ViT-B 40.02 -> 39.52 ms (weight gradients 10.0 -> 9.4 ms), ResNet-50 21.00 -> 20.95 ms; 70 is ResNet-50 21.60 ms.
-    // SAICV_TN_SLOTS_PCT overrides (read per call; e.g. 85 for a torch.distributed process group without the native communicator).
-    const char* slots_env = getenv("SAICV_TN_SLOTS_PCT");
-    const int slots_pct = slots_env ? atoi(slots_env) : (g_saicv_comm_world > 1 ? 85 : 100);
-    int splits = ((big ? 256 : 512) * slots_pct / 100) / tiles;
-    if (splits > total_rt) splits = total_rt;
-    if (splits < 1) splits = 1;
-    int rt_per = (total_rt + splits - 1) / splits;
-    splits = (total_rt + rt_per - 1) / rt_per;
-    p.m_per_split = rt_per * BR;
+    const TNPlan pl = tn_plan(q);
+    p.tiles_a = pl.tiles_a;
+    p.tiles_b = pl.tiles_b;
+    p.m_per_split = pl.rt_per * pl.BR;
     // deterministic mode (det.h): the splits park their tiles (and bias sums) side by side, one launch folds them in split order
-    // (not zeroed: every split owns at least one row tile -- (splits - 1) * rt_per < total_rt above -- and writes its whole tile and bias sums)
+    // (not zeroed: every split owns at least one row tile -- (splits - 1) * rt_per < total_rt in tn_plan() -- and writes its whole tile and bias sums)
     DetParts det;
-    if (det.begin(st, splits, (size_t)Cout * Kd + (dbias ? Cout : 0), "igemm_tn", /*zero=*/false)) return -1;
+    if (det.begin(st, pl.splits, (size_t)Cout * Kd + (dbias ? Cout : 0), "igemm_tn", /*zero=*/false)) return -1;
     p.det = det.sink();
-    const int rc = igemm_tn_launch(dtype, p, splits, big, ba, bb, BR, st);
+    const int rc = igemm_tn_launch(dtype, p, pl, st);
     if (rc) return rc;
     if (det.fold(dw, 0, (size_t)Cout * Kd, /*wide=*/true)) return -1;
     if (dbias && det.fold(dbias, (size_t)Cout * Kd, (size_t)Cout)) return -1;
     return 0;
 }
 
-static int igemm_tn_launch(int dtype, TNParams& p, int splits, bool big, int ba, int bb, int BR, hipStream_t st) {
-    const int OH = p.OH, OW = p.OW, R = p.R, S = p.S, stride = p.stride, pad = p.pad, H = p.H, W = p.W;
-    const int ohw = OH * OW;
-    p.d_img = BR / ohw;
-    const int rem = BR - p.d_img * ohw;
+static int igemm_tn_launch(int dtype, TNParams& p, const TNPlan& pl, hipStream_t st) {
+    const int OW = p.OW;
+    const int ohw = p.OH * OW;
+    const int splits = pl.splits, ba = pl.ba, bb = pl.bb;
+    const bool big = pl.big;
+    p.d_img = pl.BR / ohw;
+    const int rem = pl.BR - p.d_img * ohw;
     p.d_oh = rem / OW;
     p.d_ow = rem - p.d_oh * OW;
-    // bf16: the LDS-DMA ring kernel (32-row steps; SAICV_TN_DMA=0 selects the register-staged kernel for A/B runs)
-    const char* de = getenv("SAICV_TN_DMA");             // read per call
-    const int use_dma = de ? atoi(de) : 1;
-    if (use_dma && dtype == SAICV_DTYPE_BF16) {
+    if (pl.dma) {
         const int br = 32;
         p.d_img = br / ohw;
         const int rem32 = br - p.d_img * ohw;
         p.d_oh = rem32 / OW;
         p.d_ow = rem32 - p.d_oh * OW;
-        const bool plain = R == 1 && S == 1 && stride == 1 && pad == 0 && H == OH && W == OW;
+        const bool plain = pl.plain;
         if (big) return launch_tn_dma<256, 256, 2, 4>(p, splits, plain, st);
         if (ba == 64 && bb == 64) return launch_tn_dma<64, 64>(p, splits, plain, st);
         if (ba == 64) return launch_tn_dma<64, 128>(p, splits, plain, st);
@@ -1940,6 +1992,68 @@ static int igemm_tn_launch(int dtype, TNParams& p, int splits, bool big, int ba,
         if (bb == 64) return launch_tn<float, 128, 64>(p, splits, st);
         return launch_tn<float, 128, 128>(p, splits, st);
     }
+}
+
+// ---- the launch plan of a public entry point's product, for saicv_igemm_plan (no tensors, nothing launched)
+static NTProblem nt_problem_of(const saicv_plan_query* q) {
+    const saicv_conv_desc* d = &q->conv;
+    const bool out2 = q->act_mode == 1 || q->act_mode == 3;
+    switch (q->op) {
+        case SAICV_PLAN_CONV_FWD:        // saicv_conv2d_fwd / _fwd_stats
+            return {d->dtype, 0, d->H, d->W, d->C, d->OH, d->OW, d->R, d->S, d->stride, d->pad, d->N * d->OH * d->OW, d->K,
+                    d->R * d->S * d->C, d->K, q->out_f32 != 0, q->bias != 0, q->stats != 0, q->addend != 0, q->row_scale != 0, out2,
+                    q->bn_sums != 0, q->act_mode};
+        case SAICV_PLAN_CONV_DGRAD:      // saicv_conv2d_dgrad / _dgrad_add / _dgrad_fused
+            return {d->dtype, 1, d->OH, d->OW, d->K, d->H, d->W, d->R, d->S, d->stride, d->pad, d->N * d->H * d->W, d->C,
+                    d->R * d->S * d->K, d->C, false, false, false, q->addend != 0, false, false, q->bn_sums != 0, 0};
+        case SAICV_PLAN_LINEAR_FWD:      // saicv_linear_fwd / _gelu_fwd / _gelu_fwd_aux
+            return {q->dtype, 0, 1, 1, q->K, 1, 1, 1, 1, 1, 0, q->M, q->N, q->K, q->N, q->out_f32 != 0, q->bias != 0, false,
+                    q->addend != 0, q->row_scale != 0, out2, false, q->act_mode};
+        default:                         // SAICV_PLAN_LINEAR_DGRAD: saicv_linear_dgrad / _dgrad_gelu / _dgrad_mul
+            return {q->dtype, 1, 1, 1, q->N, 1, 1, 1, 1, 1, 0, q->M, q->K, q->N, q->K, false, false, false,
+                    q->addend != 0 || q->act_mode == 2 || q->act_mode == 4, false, false, false, q->act_mode};
+    }
+}
+
+int igemm_plan(const saicv_plan_query* q, saicv_plan* out) {
+    *out = saicv_plan{};
+    if (q->op == SAICV_PLAN_CONV_WGRAD || q->op == SAICV_PLAN_LINEAR_WGRAD) {
+        const saicv_conv_desc* d = &q->conv;
+        const TNProblem t = q->op == SAICV_PLAN_CONV_WGRAD
+            ? TNProblem{d->dtype, d->H, d->W, d->C, d->OH, d->OW, d->R, d->S, d->stride, d->pad, d->N * d->OH * d->OW, d->K, d->R * d->S * d->C}
+            : TNProblem{q->dtype, 1, 1, q->K, 1, 1, 1, 1, 1, 0, q->M, q->N, q->K};
+        const int epc = t.dtype == SAICV_DTYPE_BF16 ? 8 : 4;
+        SAICV_REQUIRE(t.C % epc == 0 && t.Cout % epc == 0, "igemm_tn: C=%d, Cout=%d must be multiples of %d", t.C, t.Cout, epc);
+        SAICV_REQUIRE(t.M > 0 && t.Cout > 0 && t.Kd > 0, "igemm_tn: empty problem");
+        SAICV_REQUIRE(tn_operands_fit(t), "igemm_tn: operand larger than 4 GiB (buffer addressing)");
+        const TNPlan pl = tn_plan(t);
+        out->route = SAICV_ROUTE_TN;
+        out->tile = pl.big ? 4 : (pl.ba == 128 ? 2 : 0) + (pl.bb == 128 ? 1 : 0);
+        out->bm = pl.ba; out->bn = pl.bb;
+        out->plain = pl.plain; out->out_f32 = 1; out->dma = pl.dma;
+        out->blocks = pl.tiles_a * pl.tiles_b * pl.splits;
+        out->splits = pl.splits; out->rt_per = pl.rt_per; out->total_rt = pl.total_rt; out->rows_per_step = pl.BR;
+        return 0;
+    }
+    const NTProblem n = nt_problem_of(q);
+    const int epc = n.dtype == SAICV_DTYPE_BF16 ? 8 : 4;
+    SAICV_REQUIRE(n.C % epc == 0, "igemm_nt: C=%d must be a multiple of %d", n.C, epc);
+    SAICV_REQUIRE(n.Kd % epc == 0, "igemm_nt: Kd=%d must be a multiple of %d", n.Kd, epc);
+    SAICV_REQUIRE(n.M > 0 && n.Nn > 0 && n.Kd > 0, "igemm_nt: empty problem");
+    SAICV_REQUIRE(!(n.bias && n.stats), "igemm_nt: bias and BN statistics are exclusive");
+    SAICV_REQUIRE(!(n.stats && n.out_f32), "saicv_conv2d_fwd: BN statistics need out_f32 = 0");
+    const NTPlan pl = nt_plan(n);
+    out->route = pl.route == NT_TILED ? SAICV_ROUTE_TILED : pl.route == NT_PW_STREAM ? SAICV_ROUTE_PW_STREAM : SAICV_ROUTE_PW3_STREAM;
+    out->blocks = pl.blocks;
+    out->stat_rows = pl.stat_rows;
+    if (pl.route != NT_TILED) return 0;
+    SAICV_REQUIRE(nt_operands_fit(n), "igemm_nt: operand larger than 4 GiB (buffer addressing)");
+    out->tile = pl.tile;
+    out->bm = kTiles[pl.tile].bm; out->bn = kTiles[pl.tile].bn;
+    out->kc8 = pl.kc8;
+    out->plain = pl.plain;
+    out->out_f32 = pl.f32o;
+    return 0;
 }
 
 }  // namespace saicv

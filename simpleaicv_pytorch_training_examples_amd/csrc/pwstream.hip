@@ -395,9 +395,17 @@ template <int KD, int ND, int NSPLIT>
 int launch(const PWParams& p, int blocks, bool stats, bool extras, hipStream_t st) {
     constexpr int NWAVES = NSPLIT > 4 ? NSPLIT : 4;
     dim3 grid(blocks), block(64 * NWAVES);
-    if (stats) hipLaunchKernelGGL((pw_stream_kernel<KD, ND, NSPLIT, true, false>), grid, block, 0, st, p);
-    else if (extras) hipLaunchKernelGGL((pw_stream_kernel<KD, ND, NSPLIT, false, true>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((pw_stream_kernel<KD, ND, NSPLIT, false, false>), grid, block, 0, st, p);
+    if constexpr (KD >= 256) {      // pw_stream_blocks() gives K = 256 to the fused data gradient only: no other form is compiled
+        if (stats || !extras) {
+            saicv::set_error("pw_stream: K = %d runs only as a data gradient with fused operands", KD);
+            return -1;
+        }
+        hipLaunchKernelGGL((pw_stream_kernel<KD, ND, NSPLIT, false, true>), grid, block, 0, st, p);
+    } else {
+        if (stats) hipLaunchKernelGGL((pw_stream_kernel<KD, ND, NSPLIT, true, false>), grid, block, 0, st, p);
+        else if (extras) hipLaunchKernelGGL((pw_stream_kernel<KD, ND, NSPLIT, false, true>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((pw_stream_kernel<KD, ND, NSPLIT, false, false>), grid, block, 0, st, p);
+    }
     return saicv::check_launch("pw_stream");
 }
 

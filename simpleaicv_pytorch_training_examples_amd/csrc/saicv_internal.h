@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 
 struct saicv_conv_desc;      // include/saicv_hip.h
+struct saicv_plan_query;
+struct saicv_plan;
 
 namespace saicv {
 
@@ -37,6 +39,9 @@ int igemm_nt(int dtype, int mode, const void* src, const void* wgt, void* out, c
 int igemm_tn(int dtype, const void* dy, const void* src, float* dw, int H, int W, int C, int OH,
              int OW, int R, int S, int stride, int pad, int M, int Cout, int Kd, hipStream_t st,
              float* dbias = nullptr);
+
+// igemm.hip: the launch plan of the product a public entry point would build (saicv_igemm_plan); q's descriptor is already checked
+int igemm_plan(const saicv_plan_query* q, saicv_plan* out);
 
 // pwstream.hip: weight-resident streaming kernel for small pointwise products; blocks = rows of partial statistics (0: not eligible).
 // igemm_nt launches them with the block count of its plan.

@@ -30,12 +30,48 @@ pytestmark = pytest.mark.gpu
 
 BATCH = int(os.environ.get('SAICV_TEST_BATCH', '256'))
 
-# (Cin, Cout, k, stride, Hin): the 23 distinct ResNet-50 convolutions at 224 x 224 input (stem: input packed to 8 channels)
-R50 = [(8, 64, 7, 2, 224), (64, 64, 1, 1, 56), (64, 64, 3, 1, 56), (64, 256, 1, 1, 56), (256, 64, 1, 1, 56),
-       (256, 128, 1, 1, 56), (128, 128, 3, 2, 56), (128, 512, 1, 1, 28), (256, 512, 1, 2, 56), (512, 128, 1, 1, 28),
-       (128, 128, 3, 1, 28), (512, 256, 1, 1, 28), (256, 256, 3, 2, 28), (256, 1024, 1, 1, 14), (512, 1024, 1, 2, 28),
-       (1024, 256, 1, 1, 14), (256, 256, 3, 1, 14), (1024, 512, 1, 1, 14), (512, 512, 3, 2, 14), (512, 2048, 1, 1, 7),
-       (1024, 2048, 1, 2, 14), (2048, 512, 1, 1, 7), (512, 512, 3, 1, 7)]
+# (Cin, Cout, k, stride, Hin): the 23 distinct ResNet-50 convolutions at 224 x 224 input (stem: input packed to 8 channels), each with
+# the kernel family saicv_igemm_plan must give its forward (+ statistics), data gradient and weight gradient at batch 256:
+# 'tiled BMxBN [kc8]' igemm_nt1_kernel, 'pw B' / 'pw3 B' the streaming kernels with B workgroups, 'tn BAxBB dma|reg xS' igemm_tn with S splits
+R50_PLANS = [
+    ((8, 64, 7, 2, 224), 'tiled 128x64', 'tiled 128x64', 'tn 64x128 dma x128'),
+    ((64, 64, 1, 1, 56), 'pw 512', 'pw 512', 'tn 64x64 dma x502'),
+    ((64, 64, 3, 1, 56), 'pw3 256', 'pw3 256', 'tn 64x128 dma x102'),
+    ((64, 256, 1, 1, 56), 'pw 512', 'tiled 128x64', 'tn 128x64 dma x256'),
+    ((256, 64, 1, 1, 56), 'tiled 128x64', 'pw 512', 'tn 64x128 dma x256'),
+    ((256, 128, 1, 1, 56), 'tiled 256x128', 'pw 512', 'tn 128x128 dma x256'),
+    ((128, 128, 3, 2, 56), 'tiled 256x128', 'tiled 256x128', 'tn 128x128 dma x56'),
+    ((128, 512, 1, 1, 28), 'pw 256', 'tiled 256x128', 'tn 128x128 dma x126'),
+    ((256, 512, 1, 2, 56), 'tiled 256x128', 'tiled 256x128', 'tn 128x128 dma x64'),
+    ((512, 128, 1, 1, 28), 'tiled 256x128', 'pw 256', 'tn 128x128 dma x126'),
+    ((128, 128, 3, 1, 28), 'tiled 256x128', 'tiled 256x128', 'tn 128x128 dma x56'),
+    ((512, 256, 1, 1, 28), 'tiled 256x128', 'tiled 256x128', 'tn 128x128 dma x64'),
+    ((256, 256, 3, 2, 28), 'tiled 256x128', 'tiled 256x128', 'tn 128x128 dma x14'),
+    ((256, 1024, 1, 1, 14), 'tiled 256x128', 'tiled 256x128', 'tn 128x128 dma x32'),
+    ((512, 1024, 1, 2, 28), 'tiled 256x128', 'tiled 256x128', 'tn 128x128 dma x16'),
+    ((1024, 256, 1, 1, 14), 'tiled 256x128', 'tiled 256x128', 'tn 128x128 dma x32'),
+    ((256, 256, 3, 1, 14), 'tiled 256x128', 'tiled 256x128', 'tn 128x128 dma x14'),
+    ((1024, 512, 1, 1, 14), 'tiled 256x128', 'tiled 256x128', 'tn 128x128 dma x16'),
+    ((512, 512, 3, 2, 14), 'tiled 128x128', 'tiled 128x128', 'tn 128x128 dma x3'),
+    ((512, 2048, 1, 1, 7), 'tiled 256x128', 'tiled 128x128', 'tn 128x128 dma x8'),
+    ((1024, 2048, 1, 2, 14), 'tiled 256x128', 'tiled 256x128', 'tn 128x128 dma x4'),
+    ((2048, 512, 1, 1, 7), 'tiled 128x128', 'tiled 256x128', 'tn 128x128 dma x8'),
+    ((512, 512, 3, 1, 7), 'tiled 128x128', 'tiled 128x128', 'tn 128x128 dma x3')]
+R50 = [r[0] for r in R50_PLANS]
+PLANS = {r[0]: r[1:] for r in R50_PLANS}
+
+
+def _plan_name(op, d):
+    """The kernel family the library plans for this product under the current switches, in the table's words."""
+    from simpleaicv_pytorch_training_examples_amd import _lib
+    q, pl = _lib.PlanQuery(), _lib.Plan()
+    q.op, q.conv, q.stats = op, d, int(op == _lib.PLAN_CONV_FWD)
+    _lib.check(_lib.lib().saicv_igemm_plan(ctypes.byref(q), ctypes.byref(pl)), 'plan')
+    if pl.route == _lib.ROUTE_TILED:
+        return f'tiled {pl.bm}x{pl.bn}' + (' kc8' if pl.kc8 else '')
+    if pl.route == _lib.ROUTE_TN:
+        return f'tn {pl.bm}x{pl.bn} {"dma" if pl.dma else "reg"} x{pl.splits}'
+    return f'{"pw" if pl.route == _lib.ROUTE_PW_STREAM else "pw3"} {pl.blocks}'
 
 
 def _bf(t):
@@ -52,6 +88,9 @@ def test_resnet50_conv_shapes_at_batch_256_match_cpu_fp32(shape):
 # switches are read per call, so the same oracle comparison covers them
 SWITCHED = [('SAICV_TN_DMA', '0', (256, 256, 3, 1, 14)), ('SAICV_TN_DMA', '0', (1024, 256, 1, 1, 14)),
             ('SAICV_NT_KC8', '1', (1024, 512, 1, 1, 14)), ('SAICV_NT_KC8', '1', (256, 128, 1, 1, 56))]
+# what the switch must change in the plans of PLANS (forward, data gradient, weight gradient)
+SWITCHED_PLANS = [('tiled 256x128', 'tiled 256x128', 'tn 128x128 reg x14'), ('tiled 256x128', 'tiled 256x128', 'tn 128x128 reg x32'),
+                  ('tiled 256x128 kc8', 'tiled 256x128 kc8', 'tn 128x128 dma x16'), ('tiled 256x128 kc8', 'pw 512', 'tn 128x128 dma x256')]
 
 
 @pytest.mark.timeout(900)
@@ -59,10 +98,10 @@ SWITCHED = [('SAICV_TN_DMA', '0', (256, 256, 3, 1, 14)), ('SAICV_TN_DMA', '0', (
 def test_switched_kernel_paths_at_batch_256_match_cpu_fp32(var, val, shape, monkeypatch):
     """The register-staged weight-gradient kernel and the 128-byte-K-slice forward / data-gradient kernel on every eligible launch: same oracle, same tolerances."""
     monkeypatch.setenv(var, val)
-    _conv_case(shape)
+    _conv_case(shape, SWITCHED_PLANS[SWITCHED.index((var, val, shape))])
 
 
-def _conv_case(shape):
+def _conv_case(shape, plans=None):
     from simpleaicv_pytorch_training_examples_amd import _lib, ops
     from simpleaicv_pytorch_training_examples_amd._lib import check, lib, ptr
     ci, co, k, s, h = shape
@@ -77,6 +116,9 @@ def _conv_case(shape):
     d = ops._desc(BATCH, h, h, ci, co, k, k, s, pad, dt)
     oh, ow = d.OH, d.OW
     dy = _bf(torch.randn(BATCH, co, oh, ow, generator=g)).contiguous(memory_format=torch.channels_last)
+    if BATCH == 256:            # which kernel family this comparison certifies (the table is written for BASELINE.json's batch)
+        planned = tuple(_plan_name(op, d) for op in (_lib.PLAN_CONV_FWD, _lib.PLAN_CONV_DGRAD, _lib.PLAN_CONV_WGRAD))
+        assert planned == tuple(plans or PLANS[shape]), (shape, planned)
 
     # ---- CPU fp32 oracle
     torch.set_num_threads(min(os.cpu_count() or 8, 64))

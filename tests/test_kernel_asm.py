@@ -43,8 +43,8 @@ def test_asm_fragment_reads_of_each_kernel_are_not_touched_before_their_counted_
     pw = F.assembly('pwstream.hip')
     reports = F.check(pw) + F.check(F.assembly('igemm.hip'))
     assert len([r for r in reports if 'pw_stream_kernel' in r[0]]) == 3           # the nine-tap forms: plain, + statistics, + data-gradient extras
-    # + the 32 bf16 forms of igemm_nt1_kernel and the 10 of igemm_tn_dma_kernel
-    assert len(reports) == 3 + 32 + 10, len(reports)
+    # + the 26 bf16 forms of igemm_nt1_kernel and the 10 of igemm_tn_dma_kernel
+    assert len(reports) == 3 + 26 + 10, len(reports)
     for name, n_reads, n_waits, scratch, bad in reports:
         assert n_reads >= 1 and n_waits >= 1 and scratch == 0 and not bad, (name, n_reads, n_waits, scratch, bad[:3])
     # mutation 1: the first three counted waits release two reads too few
@@ -83,7 +83,8 @@ def _igemm_kernels_expected():
                 wide = tile[:2] == (256, 256)             # bf16 output only: an fp32 output tile would not fit the epilogue LDS
                 names.add(nt1.format('DF16b', *tile, mode, False, plain, 4))
                 if not wide:
-                    names.add(nt1.format('DF16b', *tile, mode, True, plain, 4))
+                    if mode == 0:                         # bf16 data with an fp32 output: forward only (no entry point asks a data gradient for it)
+                        names.add(nt1.format('DF16b', *tile, mode, True, plain, 4))
                     names.add(nt1.format('f', *tile, mode, True, plain, 4))      # fp32 data always writes fp32
         for tile in tiles[:2]:                            # 128-byte K slices: pointwise bf16, 256-row tiles
             names.add(nt1.format('DF16b', *tile, mode, False, True, 8))
@@ -98,12 +99,13 @@ def _igemm_kernels_expected():
 
 @pytest.mark.timeout(1200)
 def test_igemm_instantiates_exactly_the_launchable_kernels():
-    """44 igemm_nt1_kernel forms (no fp32 data with a bf16 output, no fp32 output on the 256 x 256 tile), 10 igemm_tn_kernel, 10
-    igemm_tn_dma_kernel: a form the dispatch cannot reach is not compiled."""
+    """38 igemm_nt1_kernel forms (no fp32 data with a bf16 output, no fp32 output on the 256 x 256 tile, no fp32 output of a bf16
+    data gradient), 10 igemm_tn_kernel, 10 igemm_tn_dma_kernel: a form the dispatch cannot reach is not compiled
+    (tests/test_igemm_plan_host.py shows that each of them IS reached)."""
     import re
     import check_fragment_regs as F
     found = re.findall(r'^\s*\.amdhsa_kernel _ZN12_GLOBAL__N_1\d+(\S+)$', F.assembly('igemm.hip'), re.M)
     expected = _igemm_kernels_expected()
-    assert len(expected) == 64 and len([n for n in expected if n.startswith('igemm_nt1_kernel')]) == 44
+    assert len(expected) == 58 and len([n for n in expected if n.startswith('igemm_nt1_kernel')]) == 38
     assert len(found) == len(set(found))
     assert set(found) == expected, (sorted(set(found) - expected), sorted(expected - set(found)))
