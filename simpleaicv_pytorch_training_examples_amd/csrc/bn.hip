@@ -138,7 +138,8 @@ __global__ __launch_bounds__(64 * NW) void bn_finalize_fwd_kernel(const float* _
     finalize_colsum<NW>(sum, sq, P, C, c, ty, s, q);
     if (c >= C || ty != 0) return;
     const float mean = s / count;
-    float var = q / count - mean * mean;
+    // one sample per channel: the variance IS 0; q / n - mean^2 would leave the rounding of mean^2 (up to 1e-7 * mean^2) against eps
+    float var = count > 1.f ? q / count - mean * mean : 0.f;
     var = fmaxf(var, 0.f);
     const float invstd = rsqrtf(var + eps);
     mean_out[c] = mean;
@@ -203,7 +204,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ y
             float s = 0.f, q = 0.f;
             for (int r = 0; r < st.rows; ++r) { s += st.sum[(size_t)r * C + c]; q += st.sq[(size_t)r * C + c]; }
             const float mean = s / st.count;
-            const float var = fmaxf(q / st.count - mean * mean, 0.f);
+            const float var = st.count > 1.f ? fmaxf(q / st.count - mean * mean, 0.f) : 0.f;      // (one sample: exactly 0, as bn_finalize_fwd_kernel)
             const float invstd = rsqrtf(var + st.eps);
             const float g = st.gamma ? st.gamma[c] : 1.f, bt = st.beta ? st.beta[c] : 0.f;
             lsc[c] = g * invstd;

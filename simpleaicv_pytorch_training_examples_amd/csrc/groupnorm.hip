@@ -89,7 +89,7 @@ __global__ void gn_coeffs_kernel(const float* __restrict__ sums, const float* __
     float s = 0.f, q = 0.f;
     for (int k = 0; k < cpg; ++k) { s += S[g0 + k]; q += Q[g0 + k]; }
     const float mean = s / count;
-    const float var = fmaxf(q / count - mean * mean, 0.f);
+    const float var = count > 1.f ? fmaxf(q / count - mean * mean, 0.f) : 0.f;      // one element per group: exactly 0 (as csrc/bn.hip)
     const float rstd = rsqrtf(var + eps);
     const float a = rstd * (gamma ? gamma[c] : 1.f);
     ab[i] = a;
