@@ -1523,6 +1523,14 @@ int attention_stream(int dtype, int D, int which, const void* desc_ptr, hipStrea
         SAICV_REQUIRE(D == 64, "attention_stream: the relative-position bias is instantiated for head dim 64");
         SAICV_REQUIRE(p.Sh >= 1 && p.Sw >= 1 && p.Sh * p.Sw == p.Nk, "attention_stream: Sh*Sw must equal Nk");
         SAICV_REQUIRE(p.Sh + p.Sw <= 128, "attention_stream: relative-position tables too wide for LDS");
+        if (which != 0 && p.Sw != 64 && !(p.Sh + p.Sw <= 32 && p.Nk <= 256)) {
+            // generic table form (REL 3): the dQ kernel is the widest -- four operand chunks plus, per wavefront, the tables and their
+            // gradients; the launch would be refused past 160 KiB (Sh + Sw <= 126 in bf16, <= 94 in fp32)
+            const size_t es = dtype == SAICV_DTYPE_BF16 ? 2 : 4;
+            const size_t need = 4 * (size_t)SA_CHUNK * D * es + 2 * (size_t)SA_WAVES * SA_WROWS * (p.Sh + p.Sw + 2) * sizeof(float);
+            SAICV_REQUIRE(need <= (size_t)160 * 1024, "attention_stream: relative-position tables of %d + %d columns need %zu bytes of LDS in the "
+                          "backward (160 KiB available)", p.Sh, p.Sw, need);
+        }
     }
     if (dtype == SAICV_DTYPE_BF16) return sa_dispatch<bf16_t>(D, p, which, st);
     return sa_dispatch<float>(D, p, which, st);

@@ -280,11 +280,33 @@ def _ref_attention(qkv, heads, scale):
     return (attn @ v).transpose(1, 2).reshape(b, n, c)
 
 
+def _whole_head_attention(qkv, dy, heads, scale):
+    """saicv_attention_fwd / saicv_attention_bwd called directly on a packed qkv [B, N, 3C] -> (out [B, N, C], dqkv [B, N, 3C]).
+    ops_tfm.attention sends bf16 (and head dim 32, N > 256) to the streaming kernels, so the whole-head kernels of csrc/tfm.hip
+    are only certain to run through their own entry points."""
+    from simpleaicv_pytorch_training_examples_amd._lib import check, dtype_code, lib, ptr, stream
+    b, n, c3 = qkv.shape
+    c = c3 // 3
+    qkv = qkv.contiguous()
+    out = torch.full((b, n, c), float('nan'), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.full((b, heads, n), float('nan'), dtype=torch.float32, device=qkv.device)
+    dqkv = torch.full_like(qkv, float('nan'))
+    check(lib().saicv_attention_fwd(dtype_code(qkv.dtype), ptr(qkv), ptr(out), ptr(lse), b, n, heads, c // heads, float(scale), stream()),
+          'attention_fwd')
+    check(lib().saicv_attention_bwd(dtype_code(qkv.dtype), ptr(qkv), ptr(out), ptr(dy.contiguous()), ptr(lse), ptr(dqkv), b, n, heads,
+                                    c // heads, float(scale), stream()), 'attention_bwd')
+    torch.cuda.synchronize()
+    return out, dqkv
+
+
 @pytest.mark.parametrize('dt', [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize('b,n,heads', [(2, 197, 12), (3, 17, 3), (1, 256, 2), (2, 196, 4), (1, 1, 1), (2, 33, 2)])
 def test_attention(b, n, heads, dt):
     """fused attention fwd/bwd vs the reference formulation (vit.py:61-80): q k^T * scale ->
-    softmax -> @ v, including the ragged last key/query tiles (n % 32 != 0) and n = 1."""
+    softmax -> @ v, including the ragged last key/query tiles (n % 32 != 0) and n = 1.
+    Two routes, one assertion each: ops_tfm.attention as the models call it (fp32: the whole-head kernels attention_fwd_kernel /
+    attention_bwd_kernel; bf16: the streaming kernels of csrc/attn_stream.hip), and the whole-head kernels through their own
+    entry points in the same dtype (bf16 reaches attention_fwd_kernel<bf16> / attention_bwd_kernel<bf16> only this way)."""
     T = _tfm()
     g = torch.Generator().manual_seed(b * 1000 + n)
     c = heads * 64
@@ -300,14 +322,17 @@ def test_attention(b, n, heads, dt):
     tol = TOL[dt]
     assert rel_err(yd.float(), yr) < tol
     assert rel_err(qd.grad.float(), qr.grad) < tol * 2
+    yw, gw = _whole_head_attention(qkv.to(dt).cuda(), dy.to(dt).cuda(), heads, scale)
+    assert rel_err(yw.float(), yr) < tol
+    assert rel_err(gw.float(), qr.grad) < tol * 2
 
 
 @pytest.mark.parametrize('mode', ['1', '2'])
 @pytest.mark.parametrize('b,n,heads', [(2, 197, 12), (3, 17, 3), (1, 256, 2), (2, 196, 4), (1, 1, 1), (2, 33, 2)])
 def test_attention_backward_variants(b, n, heads, mode, monkeypatch):
-    """SAICV_ATTN_BWD2 = 1 / 2 (two tiles / one tile per wavefront with the lean instruction mix) against the same reference
-    gradient as the default backward, same tolerance; the switch is read per call."""
-    T = _tfm()
+    """SAICV_ATTN_BWD2 = 1 / 2 (two tiles / one tile per wavefront with the lean instruction mix: attention_bwd2_kernel<2> / <1>)
+    against the same reference gradient as the default backward, same tolerance; the switch is read per call.  The kernels are
+    bf16 whole-head ones, which ops_tfm.attention no longer selects: they are called through saicv_attention_bwd itself."""
     dt = torch.bfloat16
     g = torch.Generator().manual_seed(b * 1000 + n)
     c = heads * 64
@@ -315,10 +340,15 @@ def test_attention_backward_variants(b, n, heads, mode, monkeypatch):
     dy = _q(torch.randn(b, n, c, generator=g), dt)
     scale = 64 ** -0.5
     qr = qkv.clone().requires_grad_(True)
-    _ref_attention(qr, heads, scale).backward(dy)
+    yr = _ref_attention(qr, heads, scale)
+    yr.backward(dy)
     monkeypatch.setenv('SAICV_ATTN_BWD2', mode)
+    yw, gw = _whole_head_attention(qkv.to(dt).cuda(), dy.to(dt).cuda(), heads, scale)
+    assert rel_err(yw.float(), yr) < TOL[dt]
+    assert rel_err(gw.float(), qr.grad) < TOL[dt] * 2
+    # and the route the models take stays indifferent to the switch
     qd = qkv.to(dt).cuda().requires_grad_(True)
-    T.attention(qd, heads, scale).backward(dy.to(dt).cuda())
+    _tfm().attention(qd, heads, scale).backward(dy.to(dt).cuda())
     torch.cuda.synchronize()
     assert rel_err(qd.grad.float(), qr.grad) < TOL[dt] * 2
 
