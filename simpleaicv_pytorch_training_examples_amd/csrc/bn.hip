@@ -22,28 +22,7 @@ namespace {
 // pass; dz, y and the mask in the backward pass) are read exactly once by these kernels: streaming loads ("nt") keep them from
 // displacing what the neighbouring kernels re-read.  Their OUTPUTS (z; dy, dres) are read by the very next kernel and keep the default
 // policy.  Same box, library A/B on the ResNet-50 step (profiles/r05_nt_experiments.md): streaming loads 21.39 -> 21.22 ms (forward) and
-// -> 21.21 ms (backward); streaming STORES lose (21.55 / 21.50 ms).  -DSAICV_BN_FWD_LD_PLAIN / _BWD_LD_PLAIN / _FWD_ST_NT / _BWD_ST_NT
-// build the other policies (scripts/build_variant_lib.py).
-#ifdef SAICV_BN_FWD_LD_PLAIN
-#define BNF_LD ld_chunk
-#else
-#define BNF_LD ld_chunk_nt
-#endif
-#ifdef SAICV_BN_FWD_ST_NT
-#define BNF_ST st_chunk_nt
-#else
-#define BNF_ST st_chunk
-#endif
-#ifdef SAICV_BN_BWD_LD_PLAIN
-#define BNB_LD ld_chunk
-#else
-#define BNB_LD ld_chunk_nt
-#endif
-#ifdef SAICV_BN_BWD_ST_NT
-#define BNB_ST st_chunk_nt
-#else
-#define BNB_ST st_chunk
-#endif
+// -> 21.21 ms (backward); streaming STORES lose (21.55 / 21.50 ms).
 
 constexpr int kMaxBlocks = 1024;        // four 256-thread blocks per CU (sweep 512..16384: flat within 1 %, 2048 the slowest)
 
@@ -119,6 +98,8 @@ DEVINL void finalize_colsum(const float* __restrict__ a, const float* __restrict
     for (int w = 0; w < NW; ++w) { sa += la[w][x]; sb += lb[w][x]; }
 }
 constexpr int kFinalizeDirect = 1024;    // partial rows a finalize kernel takes without a reduction launch
+constexpr int kBwdMaxSlabs = 512;        // partial rows of bn_bwd_reduce at most (sweep: 256..2048)
+constexpr int kBwdMinPasses = 16;        // row passes per partial of bn_bwd_reduce at least
 
 // ---------------------------------------------------------------- forward finalize
 // Follows torch.nn.BatchNorm2d training semantics (biased var for normalisation, unbiased
@@ -244,9 +225,9 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ y
     for (size_t i = first; i < nchunks; i += stride) {
         if (!HOIST) load_coeffs((int)((i * N) % (size_t)C));
         float v[N];
-        Chunk<T>::unpack(BNF_LD(y + i * N), v);
+        Chunk<T>::unpack(ld_chunk_nt(y + i * N), v);
         float rr[N];
-        if (RES) Chunk<T>::unpack(BNF_LD(res + i * N), rr);
+        if (RES) Chunk<T>::unpack(ld_chunk_nt(res + i * N), rr);
         unsigned bits = 0;
 #pragma unroll
         for (int j = 0; j < N; ++j) {
@@ -258,7 +239,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ y
             }
             v[j] = o;
         }
-        BNF_ST(z + i * N, Chunk<T>::pack(v));
+        st_chunk(z + i * N, Chunk<T>::pack(v));
         if (RELU && mask != nullptr) mask[i] = (uint8_t)bits;     // one bit per element: all backward needs of z
     }
 }
@@ -439,8 +420,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     for (size_t i = first; i < nchunks; i += stride) {
         if (!HOIST) load_coeffs((int)((i * N) % (size_t)C));
         float g[N], yy[N], zz[N], o[N];
-        Chunk<T>::unpack(BNB_LD(dz + i * N), g);
-        Chunk<T>::unpack(BNB_LD(y + i * N), yy);
+        Chunk<T>::unpack(ld_chunk_nt(dz + i * N), g);
+        Chunk<T>::unpack(ld_chunk_nt(y + i * N), yy);
         unsigned bits = 0xffu;
         if (RELU) {
             if (mask != nullptr) {
@@ -458,23 +439,21 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
             g[j] = gj;
             o[j] = fmaf(ka[j], gj, fmaf(kb[j], yy[j], kc[j]));
         }
-        BNB_ST(dy + i * N, Chunk<T>::pack(o));
-        if (RES) BNB_ST(dres + i * N, Chunk<T>::pack(g));
+        st_chunk(dy + i * N, Chunk<T>::pack(o));
+        if (RES) st_chunk(dres + i * N, Chunk<T>::pack(g));
     }
 }
 
 inline int stream_grid(size_t nchunks) {
     size_t b = (nchunks + 255) / 256;
-    static const int cap = getenv("SAICV_BN_BLOCKS") ? atoi(getenv("SAICV_BN_BLOCKS")) : kMaxBlocks;     // tuning aid
-    if (b > (size_t)cap) b = cap;
+    if (b > (size_t)kMaxBlocks) b = kMaxBlocks;
     if (b < 1) b = 1;
     return (int)b;
 }
 
 // reduce [P][C] partial pairs down to at most 32 rows (in place into ws), returns new P
 int reduce_partials(const float*& a, const float*& b, int P, int C, float* ws, hipStream_t st) {
-    static const int direct = getenv("SAICV_BN_DIRECT") ? atoi(getenv("SAICV_BN_DIRECT")) : kFinalizeDirect;   // tuning aid
-    if (P <= direct) return P;
+    if (P <= kFinalizeDirect) return P;
     const int Y = 32;
     const int rows_per = (P + Y - 1) / Y;
     const int y_used = (P + rows_per - 1) / rows_per;
@@ -584,12 +563,10 @@ int bn_bwd_slabs(size_t M, int C, int dtype) {
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     const int cpr = C / n;
     const int rpp = cpr >= 256 ? 1 : 256 / cpr;
-    static const int cap = getenv("SAICV_BN_SLABS") ? atoi(getenv("SAICV_BN_SLABS")) : 512;     // tuning aid (sweep: 256..2048)
-    static const int passes = getenv("SAICV_BN_PASSES") ? atoi(getenv("SAICV_BN_PASSES")) : 16;
     // >= 16 passes per slab and at most two blocks per CU: the [slabs][C] partials of a 7 x 7 x 2048 layer were a
     // third of its tensor traffic at 1024 slabs
-    size_t s = M / ((size_t)rpp * passes);
-    if (s > (size_t)cap) s = cap;
+    size_t s = M / ((size_t)rpp * kBwdMinPasses);
+    if (s > (size_t)kBwdMaxSlabs) s = kBwdMaxSlabs;
     if (s < 1) s = 1;
     return (int)s;
 }

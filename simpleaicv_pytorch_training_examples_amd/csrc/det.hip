@@ -10,9 +10,9 @@ int g_deterministic = 0;
 
 namespace {
 
-// One workspace per stream that ever ran a deterministic reduction eagerly (the step's kernels run on one stream; the optional
-// weight-gradient side stream of ops._SideStream is a second -- ops.set_deterministic switches it off).  A reduction's partials live
-// from its kernel to its fold, both on the same stream, so successive reductions of a stream reuse the same memory in stream order.
+// One workspace per stream that ever ran a deterministic reduction eagerly (the step's kernels run on one stream).  A reduction's
+// partials live from its kernel to its fold, both on the same stream, so successive reductions of a stream reuse the same memory in
+// stream order.
 // A stream that is being CAPTURED into a hipGraph (torch captures on a stream of its own) cannot allocate: every capturing stream
 // takes the one capture workspace, which is kept as large as the largest eager workspace -- the eager warm-up steps that precede a
 // capture have sized it.  Graph nodes of one capture are ordered by the capture's dependencies like launches of one stream.
@@ -193,12 +193,10 @@ int DetParts::begin(hipStream_t stream, int parts, size_t n, const char* who, bo
 int DetParts::fold(float* dst, size_t offset, size_t count, bool wide_ok) const {
     if (!s.part || count == 0) return 0;
     const bool vec = (s.n % 4 == 0) && (offset % 4 == 0) && (count % 4 == 0) && ((uintptr_t)dst % 16 == 0);
-    // SAICV_ORDERED_FOLD=chain: every fold through the one-thread chain (the r06 A/B switch: "wide" changes the association of the weight-
-    // gradient sums, "coop" must not change a bit)
-    static const bool plain = getenv("SAICV_ORDERED_FOLD") && getenv("SAICV_ORDERED_FOLD")[0] == 'c';
-    if (vec && !plain && wide_ok && nparts >= 4 * FOLD_J)
+    // ("wide" changes the association of the weight-gradient sums against the one-thread chain, "coop" does not change a bit)
+    if (vec && wide_ok && nparts >= 4 * FOLD_J)
         hipLaunchKernelGGL(det_fold4_wide_kernel, dim3((unsigned)((count / 4 + FOLD_E - 1) / FOLD_E)), dim3(256), 0, st, s.part, s.n, nparts, offset, count / 4, dst);
-    else if (vec && !plain && nparts >= COOP_CH)
+    else if (vec && nparts >= COOP_CH)
         hipLaunchKernelGGL(det_fold4_coop_kernel, dim3((unsigned)((count / 4 + COOP_E - 1) / COOP_E)), dim3(256), 0, st, s.part, s.n, nparts, offset, count / 4, dst);
     else if (vec)
         hipLaunchKernelGGL(det_fold4_kernel, dim3((unsigned)((count / 4 + 255) / 256)), dim3(256), 0, st, s.part, s.n, nparts, offset, count / 4, dst);

@@ -94,8 +94,8 @@ static unsigned long long* g_nt_timeline = nullptr;
 // they evict what the neighbouring kernels re-read (the operand panels other tiles of this launch share, the dy a weight-gradient
 // kernel reads right after the data-gradient kernel did).  Same box, library A/B (profiles/r05_nt_experiments.md): ResNet-50 21.85 ->
 // 21.27 ms per step (igemm_nt 10.82 -> 10.60, igemm_tn 4.51 -> 4.30, bn_act_fwd 2.63 -> 2.55), ViT-B 40.04 -> 39.34 ms (igemm_nt 21.39 -> 20.43).
-// -DSAICV_NT_PLAIN_STORES builds the default-policy variant (scripts/build_variant_lib.py).  (A run-time choice between the two store
-// forms does not survive the compiler: `if (flag) nontemporal_store else store` is merged into one plain store.)
+// (A run-time choice between the two store forms does not survive the compiler: `if (flag) nontemporal_store else store` is merged
+// into one plain store.)
 // Which launches stream: outputs of at least SAICV_NT_STREAM_MIN_MB MiB (p.stream_out).  The streaming form is an assembly statement --
 // a run-time choice between __builtin_nontemporal_store and a plain store does not survive the compiler (both arms are merged into ONE
 // plain store; the first build of this switch measured exactly like plain stores).  `s_nop 1`: the statement's data registers may be
@@ -103,17 +103,10 @@ static unsigned long long* g_nt_timeline = nullptr;
 DEVINL void st_chunk_stream(void* q, u32x4 v) {
     asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" ::"v"(q), "v"(v) : "memory");
 }
-#ifdef SAICV_NT_PLAIN_STORES
-#define NT_OUT_ST st_chunk
-#else
 #define NT_OUT_ST(ptr, v) do { if (stream_out) st_chunk_stream(ptr, v); else st_chunk(ptr, v); } while (0)
-#endif
-// the data gradient's fused epilogue operands (shortcut gradient, pre-BatchNorm output, two mask bytes per chunk) are read exactly once
-#ifdef SAICV_DGRAD_EPI_LD_NT
-#define NT_EPI_LD ld_chunk_nt
-#else
+// the data gradient's fused epilogue operands (shortcut gradient, pre-BatchNorm output, two mask bytes per chunk) are read exactly
+// once; streaming loads of them measured neutral, so they keep the default policy
 #define NT_EPI_LD ld_chunk
-#endif
 
 // NT kernel LDS image: one K tile = 64-byte rows = 4 chunks; chunk c of row r lives at slot
 // c ^ f((r>>2)&3), f = {0,2,3,1}.  ds_read_b128 is served in 16-lane groups that mix rows 0-3 /
@@ -1712,8 +1705,8 @@ struct TNPlan {
     bool plain;         // igemm_tn_dma_kernel: 1 x 1 / stride 1 / no padding (row m of the source is row m of the GEMM)
 };
 
-// How igemm_tn runs a product, as a pure function of the problem, of the switches SAICV_TN_BIG (read once), SAICV_TN_SLOTS_PCT and
-// SAICV_TN_DMA (read per call) and of whether the process holds a multi-rank communicator.  The launch and the plan query both ask it.
+// How igemm_tn runs a product, as a pure function of the problem, of the switches SAICV_TN_SLOTS_PCT and SAICV_TN_DMA (read per call)
+// and of whether the process holds a multi-rank communicator.  The launch and the plan query both ask it.
 TNPlan tn_plan(const TNProblem& q) {
     TNPlan pl;
     const int epc = q.dtype == SAICV_DTYPE_BF16 ? 8 : 4;
@@ -1724,11 +1717,9 @@ TNPlan tn_plan(const TNProblem& q) {
     // MFMA of the 128 x 128 geometry; used when both output dimensions fill them
     // ... when both output dimensions fill them and every workgroup keeps >= 48 reduction steps (below that the
     // 256 KiB of fp32 atomics per workgroup outweigh the gain: the small-M ResNet stages stay on 128 x 128)
-    static const int force_big = getenv("SAICV_TN_BIG") ? atoi(getenv("SAICV_TN_BIG")) : -1;
     const int big_tiles = ((Cout + 255) / 256) * ((Kd + 255) / 256);
     const int big_steps = ((M + BR - 1) / BR) / (256 / big_tiles > 0 ? 256 / big_tiles : 1);
-    const bool big = force_big >= 0 ? (force_big != 0 && Cout >= 128 && Kd >= 128)
-                                    : (Cout % 256 == 0 && Kd >= 256 && (Kd % 256 == 0 || Kd >= 1024) && big_steps >= 48);
+    const bool big = Cout % 256 == 0 && Kd >= 256 && (Kd % 256 == 0 || Kd >= 1024) && big_steps >= 48;
     pl.big = big;
     const int ba = big ? 256 : Cout <= 64 ? 64 : 128;
     const int bb = big ? 256 : Kd <= 64 ? 64 : 128;

@@ -9,15 +9,10 @@
 #include "saicv_internal.h"
 #include "det.h"
 
-// cache policy of the fused optimizer kernels (library variant for A/B runs: -DSAICV_OPT_NT = streaming loads and stores: every
-// value is read once and written once per step)
-#ifdef SAICV_OPT_NT
-#define OPT_LD(ptr) __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ptr))
-#define OPT_ST(ptr, v) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(ptr))
-#else
+// cache policy of the fused optimizer kernels: the default one (streaming loads and stores -- every value is read once and written
+// once per step -- measured neutral)
 #define OPT_LD(ptr) (*reinterpret_cast<const f32x4*>(ptr))
 #define OPT_ST(ptr, v) (*reinterpret_cast<f32x4*>(ptr) = (v))
-#endif
 
 namespace {
 

@@ -610,9 +610,8 @@ int bn_relu_maxpool_bwd(int dtype, const void* dout, const uint8_t* idx, const v
     SAICV_REQUIRE(K <= 2 * stride + 1, "bn_relu_maxpool_bwd: K=%d, stride=%d: more than 2 x 2 windows cover a pixel", K, stride);
     if (hipMemsetAsync(ws, 0, 2 * (size_t)C * sizeof(float), st) != hipSuccess) { set_error("bn_relu_maxpool_bwd: memset failed"); return -1; }
     const size_t total = (size_t)Nimg * H * W * (C / n), ptotal = (size_t)Nimg * OH * OW * (C / n);
-    // the stem's own geometry: one thread per 2 x 2 pixel block (SAICV_POOL_APPLY_QUAD=0: the per-pixel form, for the A/B)
-    static const bool quad_ok = !(getenv("SAICV_POOL_APPLY_QUAD") && atoi(getenv("SAICV_POOL_APPLY_QUAD")) == 0);
-    const bool k3s2 = quad_ok && K == 3 && stride == 2 && pad == 1 && OH == (H + 1) / 2 && OW == (W + 1) / 2;
+    // the stem's own geometry: one thread per 2 x 2 pixel block (any other window geometry: the per-pixel form)
+    const bool k3s2 = K == 3 && stride == 2 && pad == 1 && OH == (H + 1) / 2 && OW == (W + 1) / 2;
     const size_t qtotal = (size_t)Nimg * ((H + 1) / 2) * ((W + 1) / 2) * (C / n);
     DetParts det;
     if (det.begin(st, sgrid(ptotal), (size_t)2 * C, "bn_relu_maxpool_bwd")) return -1;

@@ -386,10 +386,7 @@ __global__ __launch_bounds__(64 * pw_nwaves(NSPLIT, TAPS)) void pw_stream_kernel
 struct PWShape { int kd, nd, nsplit; };
 constexpr PWShape kShapes[] = {{64, 64, 1}, {64, 256, 4}, {256, 64, 1}, {128, 128, 2}, {128, 512, 8}, {128, 256, 4}};
 
-int blocks_per_cu() {
-    static const int v = getenv("SAICV_PW_BPC") ? atoi(getenv("SAICV_PW_BPC")) : 2;
-    return v < 1 ? 1 : v > 8 ? 8 : v;
-}
+constexpr int kBlocksPerCu = 2;         // workgroups of pw_stream_kernel per CU (the launch is one resident round)
 
 template <int KD, int ND, int NSPLIT>
 int launch(const PWParams& p, int blocks, bool stats, bool extras, hipStream_t st) {
@@ -432,7 +429,7 @@ int launch_taps9(const PWParams& p, int blocks, bool stats, bool extras, hipStre
 namespace saicv {
 
 // Workgroups (= rows of partial statistics) of the streaming launch for a pointwise bf16 product [M][Kd] x [Nn][Kd]^T, 0 if this
-// product stays on the tiled kernel (fused_dgrad: a data gradient with a shortcut addend or BatchNorm-backward sums).  A pure function of its arguments and of SAICV_PW_STREAM / SAICV_PW_MIN_ROWS / SAICV_PW_BPC.
+// product stays on the tiled kernel (fused_dgrad: a data gradient with a shortcut addend or BatchNorm-backward sums).  A pure function of its arguments and of SAICV_PW_STREAM / SAICV_PW_MIN_ROWS.
 int pw_stream_blocks(int dtype, int M, int Nn, int Kd, bool fused_dgrad) {
     const char* es = getenv("SAICV_PW_STREAM");           // (read per call: tests and tuning sweeps flip them in-process)
     const char* er = getenv("SAICV_PW_MIN_ROWS");
@@ -448,7 +445,7 @@ int pw_stream_blocks(int dtype, int M, int Nn, int Kd, bool fused_dgrad) {
         const int gpb = nwaves / s.nsplit;
         const int mtiles = (M + 15) / 16;
         const int want = (mtiles + gpb - 1) / gpb;
-        const int cap = 256 * blocks_per_cu() * 4 / nwaves;
+        const int cap = 256 * kBlocksPerCu * 4 / nwaves;
         return want < cap ? want : cap;
     }
     return 0;

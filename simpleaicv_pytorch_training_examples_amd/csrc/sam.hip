@@ -9,7 +9,6 @@
 //    gradient into q and into the two tables.  0.8 % of the attention flops: plain fp32 FMA kernels with the
 //    table rows in LDS, replacing four strided batched GEMM dispatches, two gathers and two index_adds.
 // All are HBM / latency bound; activations are bf16 (perf mode) or fp32 (parity mode).
-#include <stdlib.h>
 #include "common.h"
 #include "saicv_internal.h"
 #include "det.h"
@@ -648,16 +647,11 @@ int relpos_fwd(int dtype, const void* q, long q_rs, long q_bs, const float* tab_
     RelPosParams p = {};
     if (relpos_fill(p, "relpos_fwd", dtype, q, q_rs, q_bs, tab_h, tab_w, B, heads, Sh, Sw)) return -1;
     p.rel_h = rel_h; p.rel_w = rel_w;
-    const size_t smem = (size_t)(Sh + 2 * Sw - 1) * RP_PITCH * sizeof(float);
-    static const int use_mfma = getenv("SAICV_RELPOS_MFMA") ? atoi(getenv("SAICV_RELPOS_MFMA")) : 1;
-    if (dtype == SAICV_DTYPE_BF16 && use_mfma) {
+    if (dtype == SAICV_DTYPE_BF16) {
         const size_t smem_m = (size_t)(((Sh + 15) & ~15) + ((2 * Sw - 1 + 15) & ~15)) * 128;
         hipLaunchKernelGGL(relpos_fwd_mfma_kernel, dim3(Sh, B), dim3(RP_THREADS), smem_m, st, p);
-    } else if (dtype == SAICV_DTYPE_BF16) {
-        auto k = relpos_fwd_kernel<bf16_t>;
-        static bool once = (rp_allow_lds(k), true); (void)once;
-        hipLaunchKernelGGL(k, dim3(Sh, B), dim3(RP_THREADS), smem, st, p);
     } else {
+        const size_t smem = (size_t)(Sh + 2 * Sw - 1) * RP_PITCH * sizeof(float);
         auto k = relpos_fwd_kernel<float>;
         static bool once = (rp_allow_lds(k), true); (void)once;
         hipLaunchKernelGGL(k, dim3(Sh, B), dim3(RP_THREADS), smem, st, p);
@@ -703,11 +697,10 @@ int relpos_bwd(int dtype, const void* q, void* dq, long q_rs, long q_bs, const f
         else { auto k2 = relpos_bwd_tab_kernel<TT, 8, 8>; static bool o3 = (rp_allow_lds(k2), true); (void)o3;                                \
             hipLaunchKernelGGL(k2, dim3(Sh, B), dim3(RP_THREADS), (size_t)(RP_TILE * RP_PITCH + RP_TILE * 128 + RP_TILE * (64 + 128)) * sizeof(float) + 3 * RP_TILE * sizeof(int), st, p); } \
     } while (0)
-    static const int use_mfma = getenv("SAICV_RELPOS_MFMA") ? atoi(getenv("SAICV_RELPOS_MFMA")) : 1;
     if (dtype == SAICV_DTYPE_BF16) {
-        if (use_mfma && Sh == 64 && Sw == 64) {
+        if (Sh == 64 && Sw == 64) {
             hipLaunchKernelGGL((relpos_bwd_dq_mfma_kernel<2, 4>), dim3(Sh, B), dim3(RP_THREADS), 0, st, p);
-        } else if (use_mfma && Sh <= 16 && Sw <= 16) {
+        } else if (Sh <= 16 && Sw <= 16) {
             hipLaunchKernelGGL((relpos_bwd_dq_mfma_kernel<1, 1>), dim3(Sh, B), dim3(RP_THREADS), 0, st, p);
         } else {
             auto k1 = relpos_bwd_dq_kernel<bf16_t>;
@@ -715,8 +708,8 @@ int relpos_bwd(int dtype, const void* q, void* dq, long q_rs, long q_bs, const f
             hipLaunchKernelGGL(k1, dim3(Sh, B), dim3(RP_THREADS), smem1, st, p);
         }
         if (dtab_h) {
-            if (use_mfma && Sh == 64 && Sw == 64) hipLaunchKernelGGL((relpos_bwd_tab_mfma_kernel<2, 4, 8>), dim3(Sh, B), dim3(RP_THREADS), 0, st, p);
-            else if (use_mfma && Sh <= 16 && Sw <= 16) hipLaunchKernelGGL((relpos_bwd_tab_mfma_kernel<1, 1, 2>), dim3(Sh, B), dim3(RP_THREADS), 0, st, p);
+            if (Sh == 64 && Sw == 64) hipLaunchKernelGGL((relpos_bwd_tab_mfma_kernel<2, 4, 8>), dim3(Sh, B), dim3(RP_THREADS), 0, st, p);
+            else if (Sh <= 16 && Sw <= 16) hipLaunchKernelGGL((relpos_bwd_tab_mfma_kernel<1, 1, 2>), dim3(Sh, B), dim3(RP_THREADS), 0, st, p);
             else RP_TAB(bf16_t);
         }
     } else {

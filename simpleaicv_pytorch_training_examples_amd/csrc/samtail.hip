@@ -16,7 +16,6 @@
 //
 // Bilinear rule (ATen upsample_bilinear2d, align_corners = false, scale 1/4): src = max(0.25 (d + 0.5) - 0.5, 0),
 // i0 = floor(src), i1 = min(i0 + 1, n - 1), l1 = src - i0, l0 = 1 - l1; out = l0h (l0w v00 + l1w v01) + l1h (l0w v10 + l1w v11).
-#include <stdlib.h>
 #include "common.h"
 #include "saicv_internal.h"
 #include "det.h"
@@ -246,43 +245,14 @@ __global__ __launch_bounds__(ST_THREADS) void stats_up4_kernel(const T* __restri
     }
 }
 
-// d loss / d low[b, m, i, j]: the 8 x 8 output pixels around (4i, 4j) are re-interpolated from the 5 x 5 low-resolution
-// neighbourhood (L1 / L2 resident), their loss gradient evaluated and weighted -- no full-resolution gradient tensor
-template <typename T>
-__global__ __launch_bounds__(ST_THREADS) void grad_up4_kernel(const T* __restrict__ low, const float* __restrict__ targets,
-                                                               const float* __restrict__ coef, T* __restrict__ dlow, int M,
-                                                               int h, int w, float alpha, float gamma) {
-    const int bm = blockIdx.z, b = bm / M, i = blockIdx.y;
-    const int j = blockIdx.x * ST_THREADS + threadIdx.x;
-    if (j >= w) return;
-    const float c0 = coef[bm * 3], c1 = coef[bm * 3 + 1], c2 = coef[bm * 3 + 2];
-    const T* lp = low + (size_t)bm * h * w;
-    const float* tg = targets + (size_t)b * 16 * h * w;
-    float acc = 0.f;
-    for (int d = max(4 * i - 2, 0); d <= min(4 * i + 5, 4 * h - 1); ++d) {
-        const Tap th = tap4(d, h);
-        const float wh = (th.i0 == i ? th.l0 : 0.f) + (th.i1 == i ? th.l1 : 0.f);
-        if (wh == 0.f) continue;
-        const T* r0 = lp + (size_t)th.i0 * w;
-        const T* r1 = lp + (size_t)th.i1 * w;
-        for (int e = max(4 * j - 2, 0); e <= min(4 * j + 5, 4 * w - 1); ++e) {
-            const Tap tw = tap4(e, w);
-            const float ww = (tw.i0 == j ? tw.l0 : 0.f) + (tw.i1 == j ? tw.l1 : 0.f);
-            const float x = th.l0 * (tw.l0 * to_f32(r0[tw.i0]) + tw.l1 * to_f32(r0[tw.i1])) +
-                            th.l1 * (tw.l0 * to_f32(r1[tw.i0]) + tw.l1 * to_f32(r1[tw.i1]));
-            const float t = tg[(size_t)d * 4 * w + e];
-            acc = fmaf(wh * ww, loss_grad(x, t, alpha, gamma, c0, c1, c2), acc);
-        }
-    }
-    dlow[((size_t)bm * h + i) * w + j] = from_f32<T>(acc);
-}
-
-// The same gradient, tiled: a block owns 16 x 16 low-resolution pixels.  The one-thread-per-low-pixel kernel above evaluates
-// the loss gradient of every output pixel in each of the (up to four) low pixels it feeds AND once more per row / column of
-// the 8 x 8 window that only carries a zero weight -- 64 evaluations per low pixel, 4 per output pixel, each ~60 vector
-// operations with three transcendentals (1.7 ms per call at 20 x 4 x 256 x 256).  Here the 72 x 72 output pixels that touch the
-// tile are evaluated ONCE into LDS (1.27 per output pixel), from an 18 x 18 LDS copy of the low-resolution neighbourhood, and
-// each thread then gathers its 8 x 8 window with the bilinear weights.  Same formulas, same summation order.
+// d loss / d low[b, m, i, j]: the 8 x 8 output pixels around (4i, 4j) are re-interpolated from the low-resolution
+// neighbourhood, their loss gradient evaluated and weighted -- no full-resolution gradient tensor.  Tiled: a block owns
+// 16 x 16 low-resolution pixels.  One thread per low pixel on its own would evaluate the loss gradient of every output pixel in
+// each of the (up to four) low pixels it feeds AND once more per row / column of the 8 x 8 window that only carries a zero
+// weight -- 64 evaluations per low pixel, 4 per output pixel, each ~60 vector operations with three transcendentals (that form
+// measured 1.7 ms per call at 20 x 4 x 256 x 256).  Here the 72 x 72 output pixels that touch the tile are evaluated ONCE into
+// LDS (1.27 per output pixel), from an 18 x 18 LDS copy of the low-resolution neighbourhood, and each thread then gathers its
+// 8 x 8 window with the bilinear weights.
 constexpr int GU_T = 16;                  // low-resolution tile edge
 constexpr int GU_H = 4 * GU_T + 8;        // output pixels touching the tile, per axis (72)
 template <typename T>
@@ -400,20 +370,11 @@ int mask_loss_grad_up4(int dtype, const void* low, const float* targets, const f
                        int w, double alpha, double gamma, hipStream_t st) {
     const int planes = B * M;
     UP4_CHECK("mask_loss_grad_up4");
-    static const int tiled = getenv("SAICV_GRAD_UP4_TILED") ? atoi(getenv("SAICV_GRAD_UP4_TILED")) : 1;
-    if (tiled) {
-        dim3 tgrid((w + GU_T - 1) / GU_T, (h + GU_T - 1) / GU_T, planes);
-        if (dtype == SAICV_DTYPE_BF16)
-            hipLaunchKernelGGL(grad_up4_tiled_kernel<bf16_t>, tgrid, dim3(GU_T * GU_T), 0, st, (const bf16_t*)low, targets, coef, (bf16_t*)dlow, M, h, w, (float)alpha, (float)gamma);
-        else
-            hipLaunchKernelGGL(grad_up4_tiled_kernel<float>, tgrid, dim3(GU_T * GU_T), 0, st, (const float*)low, targets, coef, (float*)dlow, M, h, w, (float)alpha, (float)gamma);
-        return check_launch("mask_loss_grad_up4");
-    }
-    dim3 grid((w + ST_THREADS - 1) / ST_THREADS, h, planes);
+    dim3 tgrid((w + GU_T - 1) / GU_T, (h + GU_T - 1) / GU_T, planes);
     if (dtype == SAICV_DTYPE_BF16)
-        hipLaunchKernelGGL(grad_up4_kernel<bf16_t>, grid, dim3(ST_THREADS), 0, st, (const bf16_t*)low, targets, coef, (bf16_t*)dlow, M, h, w, (float)alpha, (float)gamma);
+        hipLaunchKernelGGL(grad_up4_tiled_kernel<bf16_t>, tgrid, dim3(GU_T * GU_T), 0, st, (const bf16_t*)low, targets, coef, (bf16_t*)dlow, M, h, w, (float)alpha, (float)gamma);
     else
-        hipLaunchKernelGGL(grad_up4_kernel<float>, grid, dim3(ST_THREADS), 0, st, (const float*)low, targets, coef, (float*)dlow, M, h, w, (float)alpha, (float)gamma);
+        hipLaunchKernelGGL(grad_up4_tiled_kernel<float>, tgrid, dim3(GU_T * GU_T), 0, st, (const float*)low, targets, coef, (float*)dlow, M, h, w, (float)alpha, (float)gamma);
     return check_launch("mask_loss_grad_up4");
 }
 

@@ -15,12 +15,8 @@
 #include "common.h"
 #include "saicv_internal.h"
 
-// cache policy of the LayerNorm kernels' loads (library variant for A/B runs: -DSAICV_LN_LD_NT = streaming loads)
-#ifdef SAICV_LN_LD_NT
-#define LN_LD ld_chunk_nt
-#else
+// cache policy of the LayerNorm kernels' loads: the default one (streaming loads measured neutral)
 #define LN_LD ld_chunk
-#endif
 
 namespace {
 
@@ -1153,7 +1149,7 @@ int dropout_add_layernorm_fwd(int dtype, const void* x, const void* branch, doub
 static int ln_bwd_blocks(int M, int* rows_per) {
     // one block of 8 wavefronts per CU, each wavefront streaming its rows with a one-row prefetch: more, smaller
     // blocks were measured slower (start-up latency and dgamma / dbeta partial rows per block)
-    static const int target = getenv("SAICV_LN_BWD_BLOCKS") ? atoi(getenv("SAICV_LN_BWD_BLOCKS")) : 256;
+    constexpr int target = 256;
     int rp = (M + LNB_WAVES * target - 1) / (LNB_WAVES * target);
     if (rp < 1) rp = 1;
     *rows_per = rp;

@@ -155,7 +155,6 @@ class FlatArena:
         return m
 
     def zero_grad(self):
-        ops.join_side_stream()
         self.flat_grad.zero_()
         self.arrived = [False] * len(self.params)
         for cb in self.zero_listeners:
@@ -231,14 +230,12 @@ class _FlatOptimizer:
 
     def check_finite(self):
         """found_inf[0] = 1 if any gradient is inf / nan (device side, no host sync)."""
-        ops.join_side_stream()
         self.found_inf.zero_()
         check(lib().saicv_grad_stats(ptr(self.arena.flat_grad), self.arena.total, ptr(self.found_inf), 0,
                                      _lib.stream()), 'grad_stats')
 
     def clip_grad_norm_(self, max_norm, inv_scale=None):
         """torch.nn.utils.clip_grad_norm_ over the whole arena, fused with the unscale."""
-        ops.join_side_stream()
         self.sumsq.zero_()
         check(lib().saicv_grad_stats(ptr(self.arena.flat_grad), self.arena.total, 0, ptr(self.sumsq),
                                      _lib.stream()), 'grad_stats')
@@ -247,13 +244,11 @@ class _FlatOptimizer:
 
     def clip_grad_value_(self, clip_value, inv_scale=None):
         """torch.nn.utils.clip_grad_value_ over the whole arena, fused with the unscale (the reference unscales first)."""
-        ops.join_side_stream()
         check(lib().saicv_grad_clip_value(ptr(self.arena.flat_grad), self.arena.total, ptr(inv_scale), float(clip_value),
                                           _lib.stream()), 'grad_clip_value')
 
     def step(self, inv_scale=None, found_inf=None):
         mask = self.arena.has_grad_mask() if self.track_missing_grads else None
-        ops.join_side_stream()
         self.refresh_hyper()
         self._launch(inv_scale, found_inf, mask)
         ops.bump_weights_epoch()
@@ -553,9 +548,8 @@ class StepGraph:
                 ops._ZeroPool.zero_all()    # the statistics scratch starts a replay all-zero, whatever ran eagerly in between
                 try:
                     out = self.fn(*args)
-                except BaseException as e:      # the capture still has to END with every forked stream rejoined: a stream left
-                    failed = e                  # capturing refuses every later allocation and copy of the process
-                ops.join_side_stream()      # every forked stream rejoins before the capture ends
+                except BaseException as e:      # the capture still has to END: a stream left capturing refuses every later
+                    failed = e                  # allocation and copy of the process
         except BaseException as e:
             failed = failed or e
         if failed is not None:
@@ -851,14 +845,7 @@ class DistributedDataParallel(torch.nn.Module):
     def _reduce_bucket(self, b):
         view = self.arena.flat_grad[b['start']:b['end']]
         if self.comm is not None:
-            # weight gradients may be produced on the side stream, BatchNorm / LayerNorm / bias gradients on the compute
-            # stream: the communication stream is ordered after BOTH by recording its event on the side stream once
-            # that has waited for the compute stream -- the compute stream itself never waits here
-            side = ops.side_stream_in_use()
             producer = torch.cuda.current_stream()
-            if side is not None:
-                side.wait_stream(producer)
-                producer = side
             rsag = os.environ.get('SAICV_DDP_RSAG_MIB')
             if rsag and view.numel() * 4 >= float(rsag) * 2 ** 20 and view.numel() % self.comm.world == 0:
                 self.comm.reduce_scatter_all_gather(view, producer)
@@ -870,19 +857,9 @@ class DistributedDataParallel(torch.nn.Module):
             return
         backend = dist.get_backend(self.process_group)
         if backend == 'nccl':
-            side = ops.side_stream_in_use()
-            if side is not None:
-                # weight gradients are produced on the side stream, BatchNorm / LayerNorm / bias gradients on the
-                # compute stream: RCCL's stream is ordered after BOTH by issuing the collective from the side stream
-                # once that has waited for the compute stream -- the compute stream itself never waits here
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    w = dist.all_reduce(view, op=dist.ReduceOp.AVG, group=self.process_group, async_op=True)
-            else:
-                w = dist.all_reduce(view, op=dist.ReduceOp.AVG, group=self.process_group, async_op=True)
+            w = dist.all_reduce(view, op=dist.ReduceOp.AVG, group=self.process_group, async_op=True)
             self._works.append((w, None))
         else:
-            ops.join_side_stream()
             w = dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.process_group, async_op=True)
             self._works.append((w, view))
 
@@ -893,8 +870,6 @@ class DistributedDataParallel(torch.nn.Module):
             self.comm.allreduce_bucket(self._flags, torch.cuda.current_stream(), average=False)
             self._works.append((None, None))
         elif self.world > 1:
-            if dist.get_backend(self.process_group) != 'nccl':
-                ops.join_side_stream()
             self._works.append((dist.all_reduce(self._flags, op=dist.ReduceOp.SUM, group=self.process_group, async_op=True), None))
         self.arena.global_flags = self._flags
 

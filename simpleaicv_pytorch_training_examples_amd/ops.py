@@ -129,16 +129,9 @@ def _arena_grad(t):
     return g
 
 
-# ------------------------------------------------------------------------------ side stream for weight gradients
-# A layer's weight gradient (igemm_tn, MFMA-bound, accumulates straight into the gradient arena) has no consumer
-# until the all-reduce / optimizer, while the data-gradient -> BatchNorm-backward chain of the next layer (HBM-bound
-# streaming kernels) is on the critical path.  Launching the weight gradients on a second HIP stream lets the two
-# kinds of kernels share the GPU (and, inside a captured step graph, makes them parallel branches).
-# Measured on MI355X (r02b): neutral to -2 % on ResNet-50 / ViT-B -- both kernel families fill every CU slot by
-# themselves, so the two queues mostly alternate instead of overlapping.  Off by default; SAICV_WGRAD_SIDE=1 turns it on.
 import os as _os
 
-WGRAD_SIDE_STREAM = _os.environ.get('SAICV_WGRAD_SIDE', '0') == '1'
+# (Weight gradients on a second HIP stream were tried twice and measured neutral to -2 %: profiles/r05_nt_experiments.md.)
 # BatchNorm-backward traffic cuts in residual networks: the shortcut gradient travels as
 # (dz, ReLU-mask) instead of a masked copy, and a BatchNorm's backward reduction comes out of the epilogue of the data
 # gradient that produces its dz.  SAICV_BN_FUSE=0 restores the three-pass form (A/B runs, tests of both paths).
@@ -159,9 +152,7 @@ def set_deterministic(on=True):
     L = lib()
     prev = bool(L.saicv_set_deterministic(1 if on else 0))
     if on:
-        global WGRAD_SIDE_STREAM
         BN_INLINE = False
-        WGRAD_SIDE_STREAM = False           # (one partials workspace per stream; a forked branch of a capture would share it)
         if torch.cuda.is_available():
             check(L.saicv_deterministic_prepare(stream()), 'deterministic_prepare')
     else:
@@ -227,45 +218,6 @@ def _take_gate(t):
         _GateLedger.consume()
         t._saicv_gate = None
     return g
-_side = {'stream': None, 'dirty': False}
-
-
-class _SideStream:
-    """with _SideStream(tensors...): launches inside run on the side stream, ordered after everything already
-    enqueued on the current stream; `tensors` are kept alive for the side stream (record_stream)."""
-
-    def __init__(self, *tensors):
-        self.tensors = tensors
-
-    def __enter__(self):
-        if _side['stream'] is None:
-            _side['stream'] = torch.cuda.Stream()
-        side = _side['stream']
-        side.wait_stream(torch.cuda.current_stream())
-        for t in self.tensors:
-            if t is not None:
-                t.record_stream(side)
-        self.ctx = torch.cuda.stream(side)
-        self.ctx.__enter__()
-        _side['dirty'] = True
-        return side
-
-    def __exit__(self, *exc):
-        return self.ctx.__exit__(*exc)
-
-
-def side_stream_in_use():
-    """the side stream if weight gradients have been launched on it since the last join, else None"""
-    return _side['stream'] if _side['dirty'] else None
-
-
-def join_side_stream():
-    """Makes the current stream wait for the weight gradients launched on the side stream.  Called by every consumer
-    of the gradient arena (bucket all-reduce, inf/nan check, clipping, optimizer step) and at the end of a captured
-    step; cheap when nothing is pending."""
-    if _side['dirty']:
-        torch.cuda.current_stream().wait_stream(_side['stream'])
-        _side['dirty'] = False
 
 
 def compute_dtype():
@@ -355,7 +307,6 @@ def pack_input(x, dtype=None, cp=8):
     return out.permute(0, 3, 1, 2)
 
 
-STEM_S2D = _os.environ.get('SAICV_STEM_S2D', '1') == '1'
 # the convolution + BatchNorm shortcut of a residual block hands its raw output to the block's join, which applies the
 # shortcut's BatchNorm in the same pass as the main branch's (one write + one read of the widest tensor of the block less);
 # SAICV_DS_JOIN_FUSE=0 materialises the normalised shortcut as before
@@ -369,7 +320,7 @@ def pack_stem_input(x, conv, dtype=None):
     reference resnet.py:172-174) the space-to-depth image of saicv_pack_input_s2d -- the convolution then runs as a
     stride-1 (K+1)/2-tap one with 4C (padded to 16) channels, K dimension 256 instead of 392 -- else pack_input()."""
     k = conv.kernel_size[0]
-    if (STEM_S2D and not x.requires_grad and conv.stride == (2, 2) and conv.kernel_size[0] == conv.kernel_size[1] and k % 2 == 1
+    if (not x.requires_grad and conv.stride == (2, 2) and conv.kernel_size[0] == conv.kernel_size[1] and k % 2 == 1
             and conv.padding == (k // 2, k // 2) and conv.groups == 1 and 4 * x.shape[1] <= 16):
         require_gpu(x)
         dtype = dtype or compute_dtype()
@@ -408,7 +359,6 @@ class _PackRegistry:
     """Compute-dtype copies of every parameter that went through packed_weight(), refreshed by ONE batched launch
     (saicv_pack_weight_batched) the first time one of them is asked for after the optimizer changed the weights, instead of
     one launch per layer and step.  The copies keep their storage, so a captured step replays against the same pointers."""
-    BATCH = _os.environ.get('SAICV_PACK_BATCH', '1') == '1'
     entries = {}            # (id(param), dtype, cin_padded, cout_padded) -> dict
     table = None            # (signature, device descriptor tensor, n, total tiles, dtype)
     # Descriptor tables a CAPTURED step launched with.  The graph keeps the table's device ADDRESS; the table itself was built in the
@@ -522,7 +472,7 @@ def packed_weight(weight, dtype, cin_padded, need_wd, cout_padded=None):
     Returns (wf [Op][R][S][Ip], wd [I][R][S][Op] or None); rows/cols beyond O are zero."""
     cout_padded = cout_padded or weight.shape[0]
     rows = getattr(weight, '_saicv_rows_of', None)          # (parameter, r0, r1): ops_tfm.LinearRowsFn
-    if _PackRegistry.BATCH and weight.is_cuda and (isinstance(weight, torch.nn.Parameter) or rows is not None):
+    if weight.is_cuda and (isinstance(weight, torch.nn.Parameter) or rows is not None):
         e = _PackRegistry.get(weight, dtype, cin_padded, cout_padded, need_wd, rows)
         if e['key'] != ((weight if rows is None else rows[0])._version, _weights_epoch[0], weight.data_ptr()):
             _PackRegistry.refresh()
@@ -889,15 +839,9 @@ class ConvBnActFn(torch.autograd.Function):
                       weight.is_contiguous(memory_format=torch.channels_last))
             # KRSC fp32 gradient: straight into the arena (atomics accumulate), else a temporary
             dw = gw if direct else torch.zeros((k, d.R, d.S, c), dtype=torch.float32, device=dev)
-            if direct and WGRAD_SIDE_STREAM:
-                with _SideStream(dy, x):
-                    t0 = KernelTimer.begin('igemm_tn')
-                    check(L.saicv_conv2d_wgrad(ctypes.byref(d), ptr(dy), ptr(x), ptr(dw), stream()), 'conv2d_wgrad')
-                    KernelTimer.end(t0, 'igemm_tn', flops, 0)
-            else:
-                t0 = KernelTimer.begin('igemm_tn')
-                check(L.saicv_conv2d_wgrad(ctypes.byref(d), ptr(dy), ptr(x), ptr(dw), st), 'conv2d_wgrad')
-                KernelTimer.end(t0, 'igemm_tn', flops, 0)
+            t0 = KernelTimer.begin('igemm_tn')
+            check(L.saicv_conv2d_wgrad(ctypes.byref(d), ptr(dy), ptr(x), ptr(dw), st), 'conv2d_wgrad')
+            KernelTimer.end(t0, 'igemm_tn', flops, 0)
             if not direct:
                 dwt = _weight_grad_s2d(dw, weight, c, gw) if ctx.s2d is not None else _weight_grad(dw, weight, c)
         return (dx, dwt, dgamma if ctx.needs_input_grad[2] else None,
@@ -1062,21 +1006,15 @@ class ConvFn(torch.autograd.Function):
             gw = _arena_grad(weight)
             direct = gw is not None and c == weight.shape[1] and weight.is_contiguous(memory_format=torch.channels_last)
             dw = gw if direct else torch.zeros((k, d.R, d.S, c), dtype=torch.float32, device=x.device)
-            if direct and WGRAD_SIDE_STREAM:
-                with _SideStream(dy, x):
-                    t0 = KernelTimer.begin('igemm_tn')
-                    check(L.saicv_conv2d_wgrad(ctypes.byref(d), ptr(dy), ptr(x), ptr(dw), stream()), 'conv2d_wgrad')
-                    KernelTimer.end(t0, 'igemm_tn', flops, 0)
-            else:
-                t0 = KernelTimer.begin('igemm_tn')
-                # the bias gradient rides along: column sums of the dY tiles the weight-gradient kernel already holds
-                check(L.saicv_conv2d_wgrad_bias(ctypes.byref(d), ptr(dy), ptr(x), ptr(dw), ptr(tb), st), 'conv2d_wgrad')
-                KernelTimer.end(t0, 'igemm_tn', flops, 0)
-                bias_done = want_b
+            t0 = KernelTimer.begin('igemm_tn')
+            # the bias gradient rides along: column sums of the dY tiles the weight-gradient kernel already holds
+            check(L.saicv_conv2d_wgrad_bias(ctypes.byref(d), ptr(dy), ptr(x), ptr(dw), ptr(tb), st), 'conv2d_wgrad')
+            KernelTimer.end(t0, 'igemm_tn', flops, 0)
+            bias_done = want_b
             if not direct:
                 dwt = _weight_grad(dw, weight, c)
         if want_b:
-            if not bias_done:                   # no weight gradient wanted (or it ran on the side stream): its own pass
+            if not bias_done:                   # no weight gradient wanted: its own pass
                 check(L.saicv_colsum(dtype_code(dt), ptr(dy), M, k, ptr(tb), st), 'colsum')
             if gb is None:
                 db = tb

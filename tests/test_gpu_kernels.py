@@ -633,7 +633,6 @@ def test_stem_on_the_space_to_depth_image_equals_the_strided_convolution(hw, dt)
     with torch.no_grad():
         conv_d.weight.copy_(wq)
     conv_d.weight.data = conv_d.weight.data.contiguous(memory_format=torch.channels_last)
-    assert ops.STEM_S2D
     with torch.autocast('cuda', dtype=torch.bfloat16, enabled=dt == torch.bfloat16):
         xp = ops.pack_stem_input(x.cuda(), conv_d, dt)
         assert getattr(xp, '_saicv_s2d', None) is not None and xp.shape[1] == 16

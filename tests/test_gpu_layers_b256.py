@@ -186,7 +186,6 @@ def test_s2d_stem_at_batch_256_matches_cpu_fp32(dt):
         bn.weight.copy_(gamma)
         bn.bias.copy_(beta)
     conv.weight.data = conv.weight.data.contiguous(memory_format=torch.channels_last)
-    assert ops.STEM_S2D
     with torch.autocast('cuda', dtype=torch.bfloat16, enabled=dt == torch.bfloat16):
         xp = ops.pack_stem_input(x.cuda(), conv, dt)
         assert getattr(xp, '_saicv_s2d', None) is not None and xp.shape[1] == 16
