@@ -327,6 +327,21 @@ int saicv_sgd_flat(float* p, const float* g, float* mom, const int32_t* block_gr
 int saicv_adamw_flat(float* p, const float* g, float* m, float* v, const int32_t* block_group,
                      const float* hyper, const float* inv_scale, const float* found_inf,
                      const uint8_t* has_grad, float* step_blk, size_t n, void* stream);
+/* Muon (reference tools/muon_optimizer.py) on the flat arenas.  `tab`: 13 int32 per Muon parameter (workspace offsets, padded and
+ * true sizes, tile-count prefix sums, first arena block, storage columns, transposed flag, lr ratio as float bits, offset into
+ * the diagonal residuals `da` / `db`, one float per padded row; filled by ops.MuonPlan); `block_prob`: per 1024-element block the problem index, -1 = AdamW-backup block, -2 = not stepped;
+ * `hyper`: lr, wd, momentum, nesterov, beta1, beta2, eps, 1-beta1, 1-beta2.  prepare: backup blocks take the reference's own
+ * AdamW update, Muon blocks update the momentum buffer (s1) and write bf16(v) into the packed operand workspace `xws`.
+ * newton_schulz: the operand in x0 -> NS(operand), left in x0 for an even `steps`, in x1 for an odd one; 3 launches per step
+ * for ALL problems (+2 when `normalize`; `partials`: 32 floats per problem).  apply: p = p (1 - lr wd) - lr ratio u. */
+int saicv_muon_prepare(float* p, const float* g, float* s1, float* s2, const int32_t* block_prob, const int32_t* tab,
+                       const float* hyper, const float* inv_scale, const float* found_inf, const uint8_t* has_grad,
+                       float* step_blk, void* xws, size_t n, void* stream);
+int saicv_muon_newton_schulz(void* x0, void* x1, void* amat, void* bmat, float* da, float* db, const int32_t* tab, int nprob, int tiles_sym,
+                             int tiles_full, int steps, double a, double b, double c, int normalize, float* partials,
+                             void* stream);
+int saicv_muon_apply(float* p, const void* uws, const int32_t* block_prob, const int32_t* tab, const float* hyper,
+                     const float* found_inf, const uint8_t* has_grad, size_t n, void* stream);
 int saicv_grad_stats(const float* g, size_t n, float* found_inf, float* sumsq, void* stream);
 int saicv_grad_clip_scale(float* g, size_t n, const float* sumsq, const float* inv_scale,
                           double max_norm, void* stream);

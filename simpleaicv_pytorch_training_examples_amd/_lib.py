@@ -140,6 +140,9 @@ SIGNATURES = {
     'saicv_scale_by_scalar': (c_int, [c_int, _P, _P, _P, c_size_t, _P]),
     'saicv_sgd_flat': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     'saicv_adamw_flat': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'saicv_muon_prepare': (c_int, [_P] * 12 + [c_size_t, _P]),
+    'saicv_muon_newton_schulz': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_int, _P, _P]),
+    'saicv_muon_apply': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     'saicv_grad_stats': (c_int, [_P, c_size_t, _P, _P, _P]),
     'saicv_grad_clip_scale': (c_int, [_P, c_size_t, _P, _P, c_double, _P]),
     'saicv_grad_clip_value': (c_int, [_P, c_size_t, _P, c_double, _P]),

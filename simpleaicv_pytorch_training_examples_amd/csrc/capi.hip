@@ -67,6 +67,9 @@ int colsum(int, const void*, int, int, float*, hipStream_t);
 int row_scale(int, const void*, const float*, void*, size_t, int, int, hipStream_t);
 int sgd_flat(float*, const float*, float*, const int32_t*, const float*, const float*, const float*, const uint8_t*, size_t, hipStream_t);
 int adamw_flat(float*, const float*, float*, float*, const int32_t*, const float*, const float*, const float*, const uint8_t*, float*, size_t, hipStream_t);
+int muon_prepare(float*, const float*, float*, float*, const int32_t*, const int32_t*, const float*, const float*, const float*, const uint8_t*, float*, void*, size_t, hipStream_t);
+int muon_newton_schulz(void*, void*, void*, void*, float*, float*, const int32_t*, int, int, int, int, double, double, double, int, float*, hipStream_t);
+int muon_apply(float*, const void*, const int32_t*, const int32_t*, const float*, const float*, const uint8_t*, size_t, hipStream_t);
 int grad_stats(const float*, size_t, float*, float*, hipStream_t);
 int grad_clip_scale(float*, size_t, const float*, const float*, double, hipStream_t);
 int grad_clip_value(float*, size_t, const float*, double, hipStream_t);
@@ -398,6 +401,20 @@ int saicv_adamw_flat(float* p, const float* g, float* m, float* v, const int32_t
                      const float* hyper, const float* inv_scale, const float* found_inf,
                      const uint8_t* has_grad, float* step_blk, size_t n, void* stream) {
     return adamw_flat(p, g, m, v, block_group, hyper, inv_scale, found_inf, has_grad, step_blk, n, S(stream));
+}
+int saicv_muon_prepare(float* p, const float* g, float* s1, float* s2, const int32_t* block_prob, const int32_t* tab,
+                       const float* hyper, const float* inv_scale, const float* found_inf, const uint8_t* has_grad,
+                       float* step_blk, void* xws, size_t n, void* stream) {
+    return muon_prepare(p, g, s1, s2, block_prob, tab, hyper, inv_scale, found_inf, has_grad, step_blk, xws, n, S(stream));
+}
+int saicv_muon_newton_schulz(void* x0, void* x1, void* amat, void* bmat, float* da, float* db, const int32_t* tab, int nprob, int tiles_sym,
+                             int tiles_full, int steps, double a, double b, double c, int normalize, float* partials,
+                             void* stream) {
+    return muon_newton_schulz(x0, x1, amat, bmat, da, db, tab, nprob, tiles_sym, tiles_full, steps, a, b, c, normalize, partials, S(stream));
+}
+int saicv_muon_apply(float* p, const void* uws, const int32_t* block_prob, const int32_t* tab, const float* hyper,
+                     const float* found_inf, const uint8_t* has_grad, size_t n, void* stream) {
+    return muon_apply(p, uws, block_prob, tab, hyper, found_inf, has_grad, n, S(stream));
 }
 int saicv_grad_stats(const float* g, size_t n, float* found_inf, float* sumsq, void* stream) {
     return grad_stats(g, n, found_inf, sumsq, S(stream));

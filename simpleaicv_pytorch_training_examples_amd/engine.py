@@ -403,6 +403,104 @@ class AdamW(_FlatOptimizer):
                                      ptr(has_grad), ptr(self.step_blk), a.total, _lib.stream()), 'adamw_flat')
 
 
+class Muon(_FlatOptimizer):
+    """The reference's Muon (tools/muon_optimizer.py) on the flat arenas: matrices take momentum -> nesterov -> Newton-Schulz
+    orthogonalisation -> decoupled decay -> p -= lr * 0.2 sqrt(max(p.shape[:2])) * u, everything else the reference's own AdamW.
+    One param group with the reference's keys.  A step is 4 + 3 ns_steps launches whatever the number of parameters
+    (csrc/muon.hip): prepare (momentum, AdamW backup, bf16 operands), two for the ordered Frobenius norms, three grouped GEMM
+    launches per Newton-Schulz iteration, apply.  Every buffer is allocated here, nothing synchronises with the host."""
+
+    def __init__(self, model, muon_params, adamw_params=(), lr=1e-3, wd=0.1, momentum=0.95, nesterov=True, ns_steps=5,
+                 adamw_betas=(0.9, 0.999), adamw_eps=1e-8):
+        import math
+        muon_params, adamw_params = list(muon_params), list(adamw_params)
+        for p in muon_params:
+            if p.ndim < 2:
+                raise ValueError(f'Muon requires parameters with ndim >= 2, got {p.ndim}')
+        group = dict(params=muon_params + adamw_params, lr=lr, wd=wd, momentum=momentum, nesterov=nesterov, ns_steps=ns_steps,
+                     adamw_betas=tuple(adamw_betas), adamw_eps=adamw_eps)
+        super().__init__(model, [group])
+        a = self.arena
+        self._use_muon = {id(p): True for p in muon_params}
+        self._use_muon.update({id(p): False for p in adamw_params})
+        self._hyper_dev = torch.zeros(16, dtype=torch.float32, device=a.device)
+        # per block: the Muon problem index, -1 for the AdamW backup, -2 for parameters this optimizer does not step
+        table = torch.full((a.total // ALIGN,), -2, dtype=torch.int32)
+        shapes, blocks, ratios = [], [], []
+        for k, p in enumerate(muon_params + adamw_params):
+            o = a.offsets[self._pidx[id(p)]] // ALIGN
+            nb = (p.numel() + ALIGN - 1) // ALIGN
+            if k < len(muon_params):
+                # dim 0 is the outermost dimension of a contiguous and of a channels-last tensor alike: in storage order the
+                # parameter is a row-major [size(0)][numel / size(0)] matrix, its columns permuted for channels-last -- and
+                # Newton-Schulz commutes with a permutation of the columns
+                if p.stride(0) * p.shape[0] != p.numel():
+                    raise ValueError('Muon: dim 0 of a parameter must be its outermost dimension in memory')
+                table[o:o + nb] = k
+                shapes.append((p.shape[0], p.numel() // p.shape[0]))
+                blocks.append(o)
+                ratios.append(0.2 * math.sqrt(max(p.shape[0], p.shape[1])))      # the FIRST TWO dimensions, as the reference
+            else:
+                table[o:o + nb] = -1
+        self.block_prob = table.to(a.device)
+        self.plan = ops.MuonPlan(shapes, a.device, blocks, ratios)
+        self.state1 = torch.zeros_like(a.flat_param)        # Muon: momentum buffer; backup: moment1
+        self.state2 = torch.zeros_like(a.flat_param)        # backup: moment2
+        self.step_blk = torch.zeros(a.total // ALIGN, dtype=torch.float32, device=a.device)
+
+    def _reset_state(self):
+        self.state1.zero_()
+        self.state2.zero_()
+        self.step_blk.zero_()
+
+    def _state_of(self, p):
+        if self._use_muon[id(p)]:
+            return {'use_muon': True, 'momentum_buffer': self._param_view(self.state1, p).reshape(p.shape[0], -1).clone()}
+        b0 = self.arena.offsets[self._pidx[id(p)]] // ALIGN
+        step = int(self.step_blk[b0])
+        if step == 0:
+            return {'use_muon': False}
+        return {'use_muon': False, 'step': step, 'moment1': self._param_view(self.state1, p).detach().clone(),
+                'moment2': self._param_view(self.state2, p).detach().clone()}
+
+    def _load_state_of(self, p, entry):
+        if bool(entry.get('use_muon', self._use_muon[id(p)])) != self._use_muon[id(p)]:
+            raise ValueError('Muon state_dict: use_muon does not match this optimizer\'s parameter split')
+        if self._use_muon[id(p)]:
+            buf = entry.get('momentum_buffer')
+            if buf is not None:
+                if buf.numel() != p.numel() or buf.shape[0] != p.shape[0]:
+                    raise ValueError(f'momentum_buffer shape {tuple(buf.shape)} does not match parameter {tuple(p.shape)}')
+                self._param_view(self.state1, p).copy_(buf.reshape(p.shape))
+            return
+        if 'step' not in entry:
+            return
+        for key, flat in (('moment1', self.state1), ('moment2', self.state2)):
+            if tuple(entry[key].shape) != tuple(p.shape):
+                raise ValueError(f'{key} shape {tuple(entry[key].shape)} does not match parameter {tuple(p.shape)}')
+            self._param_view(flat, p).copy_(entry[key])
+        b0 = self.arena.offsets[self._pidx[id(p)]] // ALIGN
+        self.step_blk[b0:b0 + (p.numel() + ALIGN - 1) // ALIGN] = float(entry['step'])
+
+    def _hyper_rows(self):
+        g = self.param_groups[0]
+        b1, b2 = g['adamw_betas']
+        return [[g['lr'], g['wd'], g['momentum'], 1.0 if g['nesterov'] else 0.0, b1, b2, g['adamw_eps'], 1 - b1, 1 - b2,
+                 0, 0, 0, 0, 0, 0, 0]]
+
+    def _launch(self, inv_scale, found_inf, has_grad):
+        a, plan = self.arena, self.plan
+        check(lib().saicv_muon_prepare(ptr(a.flat_param), ptr(a.flat_grad), ptr(self.state1), ptr(self.state2),
+                                       ptr(self.block_prob), ptr(plan.table), ptr(self._hyper_dev), ptr(inv_scale),
+                                       ptr(found_inf), ptr(has_grad), ptr(self.step_blk), ptr(plan.x[0]), a.total,
+                                       _lib.stream()), 'muon_prepare')
+        if plan.nprob == 0:
+            return
+        buf = plan.run(self.param_groups[0]['ns_steps'])
+        check(lib().saicv_muon_apply(ptr(a.flat_param), ptr(plan.x[buf]), ptr(self.block_prob), ptr(plan.table),
+                                     ptr(self._hyper_dev), ptr(found_inf), ptr(has_grad), a.total, _lib.stream()), 'muon_apply')
+
+
 # ------------------------------------------------------------------------------ GradScaler
 class GradScaler:
     """torch.amp.GradScaler surface without host syncs: the scale lives on the device, the

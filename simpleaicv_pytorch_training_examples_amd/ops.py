@@ -1536,3 +1536,80 @@ class SoftmaxCEFn(torch.autograd.Function):
 
 def softmax_cross_entropy(logits, label, soft=False):
     return SoftmaxCEFn.apply(logits, label, soft)
+
+
+# ------------------------------------------------------------------------------ Muon: grouped Newton-Schulz (csrc/muon.hip)
+MUON_TILE = 64
+MUON_TAB = 13           # int32 per problem, the layout of csrc/muon.hip
+MUON_COEFFS = (3.4445, -4.7750, 2.0315)
+
+
+class MuonPlan:
+    """Problem table and workspaces of one set of matrices: built once, every address fixed afterwards.
+    `shapes`: (rows, cols) of each matrix in STORAGE order (row-major); `blocks`: first 1024-element arena block of each
+    (engine.Muon), `ratios`: the lr factor of each.  Workspaces hold the operand in the wide orientation, padded with zeros to
+    multiples of 64 (the padding is never written, so it stays zero)."""
+
+    def __init__(self, shapes, device, blocks=None, ratios=None):
+        import struct
+        rows, xoff, aoff, sym, full, doff = [], 0, 0, 0, 0, 0
+        self.items = []
+        for k, (r, c) in enumerate(shapes):
+            if r < 1 or c < 1:
+                raise ValueError(f'muon: matrix {k} has shape {(r, c)}')
+            tr = r > c
+            m, n = (c, r) if tr else (r, c)
+            mp, np_ = -(-m // MUON_TILE) * MUON_TILE, -(-n // MUON_TILE) * MUON_TILE
+            ratio = struct.unpack('i', struct.pack('f', float(ratios[k]) if ratios is not None else 1.0))[0]
+            rows.append([xoff, aoff, mp, np_, sym, full, blocks[k] if blocks is not None else 0, c, int(tr), ratio, m, n, doff])
+            self.items.append((xoff, mp, np_, m, n, tr))
+            tm = mp // MUON_TILE
+            xoff, aoff, sym, full = xoff + mp * np_, aoff + mp * mp, sym + tm * (tm + 1) // 2, full + tm * (np_ // MUON_TILE)
+            doff += mp
+        if max(xoff, aoff) >= 2 ** 31:
+            raise ValueError('muon: the packed workspaces exceed 2^31 elements')
+        self.nprob, self.tiles_sym, self.tiles_full = len(rows), sym, full
+        self.table = torch.tensor(rows if rows else [[0] * MUON_TAB], dtype=torch.int32).to(device)
+        self.x = [torch.zeros(max(xoff, 8), dtype=torch.bfloat16, device=device) for _ in range(2)]
+        self.a = torch.zeros(max(aoff, 8), dtype=torch.bfloat16, device=device)
+        self.b = torch.zeros(max(aoff, 8), dtype=torch.bfloat16, device=device)
+        # fp32 residuals of the diagonals of A and B (what their rounding to bf16 took away), one float per padded row
+        self.da = torch.zeros(max(doff, 1), dtype=torch.float32, device=device)
+        self.db = torch.zeros(max(doff, 1), dtype=torch.float32, device=device)
+        self.partials = torch.zeros(max(len(rows), 1) * 32, dtype=torch.float32, device=device)
+
+    def operand(self, k, buf=0):
+        """[m][n] view of problem k's operand (wide orientation, without the padding) in workspace `buf`."""
+        xoff, mp, np_, m, n, tr = self.items[k]
+        return self.x[buf][xoff:xoff + mp * np_].view(mp, np_)[:m, :n]
+
+    def run(self, steps, coeffs=MUON_COEFFS, normalize=True):
+        """Newton-Schulz on the operands in workspace 0 -> index of the workspace that holds the result."""
+        check(lib().saicv_muon_newton_schulz(ptr(self.x[0]), ptr(self.x[1]), ptr(self.a), ptr(self.b), ptr(self.da), ptr(self.db),
+                                             ptr(self.table),
+                                             self.nprob, self.tiles_sym, self.tiles_full, int(steps), float(coeffs[0]),
+                                             float(coeffs[1]), float(coeffs[2]), int(bool(normalize)), ptr(self.partials),
+                                             stream()), 'muon_newton_schulz')
+        return int(steps) & 1
+
+
+def muon_newton_schulz(tensors, steps=5, coeffs=MUON_COEFFS, normalize=True):
+    """Newton-Schulz orthogonalisation (the reference's zeropower_via_newtonschulz5) of a LIST of 2-d tensors of mixed shapes
+    in one set of grouped launches: X = bf16(t), transposed if rows > cols, X /= |X|_F + 1e-7 (if `normalize`), then `steps`
+    times A = X X^T, B = b A + c A A, X = a X + B X.  -> list of bf16 tensors, each in its input's orientation."""
+    tensors = list(tensors)
+    if not tensors:
+        return []
+    require_gpu(*tensors)
+    for t in tensors:
+        if t.dim() != 2:
+            raise ValueError(f'muon_newton_schulz takes 2-d tensors, got {tuple(t.shape)}')
+    plan = MuonPlan([tuple(t.shape) for t in tensors], tensors[0].device)
+    for k, t in enumerate(tensors):
+        plan.operand(k).copy_(t.detach().t() if plan.items[k][5] else t.detach())
+    buf = plan.run(steps, coeffs, normalize)
+    out = []
+    for k in range(len(tensors)):
+        u = plan.operand(k, buf)
+        out.append((u.t() if plan.items[k][5] else u).contiguous())
+    return out

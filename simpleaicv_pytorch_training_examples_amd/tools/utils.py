@@ -270,14 +270,47 @@ def _per_parameter_settings(config, model):
     return out
 
 
+MUON_EXCLUDE_NAMES = ['position_encoding', 'cls_token', 'patch_embedding']
+
+
+def _muon_split(config, model):
+    """-> (muon_names, adamw_names) of the trainable parameters, reference tools/utils.py:609-638: a parameter goes to Muon
+    when it has at least two dimensions and its name contains none of MUON_EXCLUDE_NAMES nor of the config's
+    `exclude_muon_layer_name_list`; everything else goes to Muon's own AdamW.  Host only."""
+    op = config.optimizer[1]
+    exclude = list(MUON_EXCLUDE_NAMES)
+    if isinstance(op.get('exclude_muon_layer_name_list'), list):
+        exclude = exclude + op['exclude_muon_layer_name_list']
+    muon_names, adamw_names = [], []
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        if p.ndim >= 2 and not any(k in name for k in exclude):
+            muon_names.append(name)
+        else:
+            adamw_names.append(name)
+    return muon_names, adamw_names
+
+
 def build_optimizer(config, model):
-    """-> (optimizer, model_layer_weight_decay_list), reference tools/utils.py:292-679 (SGD and
-    AdamW branches; Muon is outside the hot path).  Parameter groups are the distinct
-    (weight_decay, lr[, lr_scale]) combinations in first-appearance order."""
+    """-> (optimizer, model_layer_weight_decay_list), reference tools/utils.py:292-679.  SGD / AdamW: parameter groups are
+    the distinct (weight_decay, lr[, lr_scale]) combinations in first-appearance order.  Muon: ONE group with the reference's
+    keys (lr, wd, momentum, nesterov, ns_steps, adamw_betas, adamw_eps); matrices (`_muon_split`) take the Newton-Schulz
+    update of engine.Muon, the rest its AdamW backup; per-layer lr / weight-decay options are ignored as in the reference,
+    and the summary has up to two entries, Muon first."""
     optimizer_name, op = config.optimizer[0], config.optimizer[1]
     assert optimizer_name in ['SGD', 'AdamW', 'Muon'], 'Unsupported optimizer!'
     if optimizer_name == 'Muon':
-        raise NotImplementedError('Muon is only used by the universal-segmentation configs (out of scope)')
+        muon_names, adamw_names = _muon_split(config, model)
+        target = model.module if hasattr(model, 'module') else model
+        by_name = dict(model.named_parameters())
+        summary = [{'name': names, 'optimizer': which, 'lr': op['lr'], 'weight_decay': op['weight_decay']}
+                   for which, names in (('Muon', muon_names), ('AdamW', adamw_names)) if names]
+        opt = engine.Muon(target, [by_name[n] for n in muon_names], [by_name[n] for n in adamw_names], lr=op['lr'],
+                          wd=op['weight_decay'], momentum=op.get('momentum', 0.95), nesterov=op.get('nesterov', True),
+                          ns_steps=op.get('ns_steps', 5), adamw_betas=(op.get('adamw_beta1', 0.9), op.get('adamw_beta2', 0.999)),
+                          adamw_eps=op.get('adamw_eps', 1e-08))
+        return opt, summary
     settings = _per_parameter_settings(config, model)
     groups, summary, index = [], [], {}
     for name, p, wd, lr, scale in settings:
