@@ -5,6 +5,7 @@ Activations are NCHW-shaped, NHWC-strided (torch.channels_last) tensors in the c
 and every parameter gradient are fp32, as under the reference's autocast region
 (reference tools/scripts.py:153-156).
 """
+import collections
 import ctypes
 
 import torch
@@ -230,13 +231,13 @@ def compute_dtype():
     return torch.float32
 
 
-def _nhwc(x):
-    """Returns x as a dense NHWC-strided tensor (no copy when it already is)."""
+def _nhwc(x, dt=None):
+    """Returns x as a dense NHWC-strided tensor [of dtype dt] (no copy when it already is)."""
     if x.dim() != 4:
         raise ValueError('expected a 4-d NCHW-shaped tensor')
     if not x.is_contiguous(memory_format=torch.channels_last):
         x = x.contiguous(memory_format=torch.channels_last)
-    return x
+    return x if dt is None or x.dtype == dt else x.to(dt)
 
 
 def _empty_nhwc(n, c, h, w, dtype, device):
@@ -527,11 +528,335 @@ def _weight_grad_s2d(dw, weight, cq, arena_grad):
 
 
 # ------------------------------------------------------------------------------ conv + BN + act
+class _RunningStats:
+    """The running-statistics arguments of the kernels that finalise training-mode BatchNorm statistics (saicv_bn_finalize_fwd,
+    saicv_bn_act_fwd_stats, saicv_bn_act_fwd_join), worked out once per call: pointers, or 0 where nothing is tracked."""
+    __slots__ = ('mean', 'var', 'momentum', 'eps', 'nbt')
+
+    def __init__(self, bn, track):
+        if bn.momentum is None:
+            raise NotImplementedError('BatchNorm2d(momentum=None) is not supported')
+        track = track and bn.running_mean is not None
+        self.mean, self.var = (ptr(bn.running_mean), ptr(bn.running_var)) if track else (0, 0)
+        self.momentum, self.eps = float(bn.momentum), float(bn.eps)
+        self.nbt = ptr(bn.num_batches_tracked) if track else 0
+
+    def finalize(self, sums, sqs, rows, k, count, gamma, beta, mean, invstd, scale, shift, st):
+        """`rows` rows of channel sums / sums of squares -> mean, invstd, scale, shift; running statistics, num_batches_tracked += 1"""
+        L = lib()
+        ws = torch.empty(L.saicv_bn_ws_floats(k), dtype=torch.float32, device=mean.device)
+        check(L.saicv_bn_finalize_fwd(ptr(sums), ptr(sqs), rows, k, float(count), ptr(gamma), ptr(beta), self.mean, self.var,
+                                      self.momentum, self.eps, ptr(mean), ptr(invstd), ptr(scale), ptr(shift), ptr(ws), self.nbt,
+                                      st), 'bn_finalize_fwd')
+
+
+def _bn_grad_buffers(gamma, beta, k, dev):
+    """-> (dgamma, dbeta, direct_bn): both arena gradients, for the BatchNorm-backward kernels to add into, else two fresh vectors"""
+    gg, gb = _arena_grad(gamma), _arena_grad(beta)
+    if gg is not None and gb is not None:
+        return gg, gb, True
+    return torch.empty(k, dtype=torch.float32, device=dev), torch.empty(k, dtype=torch.float32, device=dev), False
+
+
+def _conv_data_grad(d, dy, weight, wd, x_shape, dt, st, fuse=None, addend=None):
+    """dx of the convolution `d` describes: the plain data gradient, + addend in its epilogue, or the fused form `fuse`
+    (a _lib.DgradFuse) asks for.  wd = None: the [I][R][S][d.K] weight copy is fetched (packed on first use) here.  st: the
+    stream, looked up once per autograd node by its forward / backward (torch.cuda.current_stream() is a ~10 us host call)."""
+    n, c, h, w = x_shape
+    if wd is None:
+        _, wd = packed_weight(weight, dt, c, True, d.K)
+    dx = _empty_nhwc(n, c, h, w, dt, dy.device)
+    L = lib()
+    if fuse is not None:
+        check(L.saicv_conv2d_dgrad_fused(ctypes.byref(d), ptr(dy), ptr(wd), ctypes.byref(fuse), ptr(dx), st), 'conv2d_dgrad_fused')
+    elif addend is not None:
+        check(L.saicv_conv2d_dgrad_add(ctypes.byref(d), ptr(dy), ptr(wd), ptr(addend), ptr(dx), st), 'conv2d_dgrad_add')
+    else:
+        check(L.saicv_conv2d_dgrad(ctypes.byref(d), ptr(dy), ptr(wd), ptr(dx), st), 'conv2d_dgrad')
+    return dx
+
+
+def _conv_weight_grad(d, dy, x, weight, st, s2d=None, bias_out=None):
+    """Weight gradient of the convolution `d` describes -> a gradient for `weight`, or None when the kernel accumulated it
+    straight into the arena (_arena_grad).  bias_out: fp32 [d.K] the same launch adds the column sums of dy into.  s2d: the input is
+    a space-to-depth image (pack_stem_input).  A `d` whose K is zero-padded beyond the weight's rows (ConvFn) gets [d.K, C, R, S]."""
+    c = d.C
+    gw = _arena_grad(weight)
+    # KRSC fp32 gradient: straight into the arena (atomics accumulate) where its view has that layout row for row -- the ONE rule
+    # for "the kernel may accumulate into p.grad", which the engine's "gradient complete" signal relies on -- else a temporary
+    direct = (gw is not None and d.K == weight.shape[0] and c == weight.shape[1]
+              and weight.is_contiguous(memory_format=torch.channels_last))
+    dw = gw if direct else torch.zeros((d.K, d.R, d.S, c), dtype=torch.float32, device=x.device)
+    L = lib()
+    if bias_out is None:
+        check(L.saicv_conv2d_wgrad(ctypes.byref(d), ptr(dy), ptr(x), ptr(dw), st), 'conv2d_wgrad')
+    else:
+        check(L.saicv_conv2d_wgrad_bias(ctypes.byref(d), ptr(dy), ptr(x), ptr(dw), ptr(bias_out), st), 'conv2d_wgrad')
+    if direct:
+        return None
+    if s2d is not None:
+        return _weight_grad_s2d(dw, weight, c, gw)
+    if d.K != weight.shape[0]:
+        return dw.permute(0, 3, 1, 2)
+    return _weight_grad(dw, weight, c)
+
+
+# what the convolution + statistics stage of ConvBnActFn.forward hands to the tail that follows it (run: _RunningStats or None)
+_ConvStage = collections.namedtuple('_ConvStage', 'x y d wd M st training inline stats rows mean invstd scale shift run eps in_link s2d')
+
+
+def _conv_stage(x, weight, gamma, beta, bn, stride, pad, need_dx, pooled, defer):
+    """Input checks, weights and descriptor (space-to-depth or ordinary), the convolution with its BatchNorm statistics, and
+    the coefficients where they are needed as tensors: scale / shift in eval mode and, with `inline` false, in training."""
+    require_gpu(x, weight)
+    # this conv's data gradient IS the dz of the BatchNorm(+ReLU) node that produced x (when x has no other consumer):
+    # it can leave that node's backward partial sums behind (the pooled block's data gradient is the plain one)
+    in_link = getattr(x, '_saicv_bn', None) if (BN_FUSE and need_dx and not pooled) else None
+    xin = x
+    x = _nhwc(x)
+    dt = x.dtype
+    n, c, h, w = x.shape
+    k, ci, r, s = weight.shape
+    if c < ci:
+        raise ValueError(f'input has {c} channels, weight expects {ci}')
+    if in_link is not None and not (x is xin and c == ci and in_link.y.shape == x.shape and in_link.y.dtype == dt):
+        in_link = None
+    s2d = getattr(xin, '_saicv_s2d', None)
+    if s2d is not None:
+        # stride-2 stem on the space-to-depth image (pack_stem_input): a stride-1 convolution with (R+1)/2 taps
+        if need_dx or (s2d[0], s2d[3], s2d[4]) != (ci, r, pad) or stride != 2 or r != s:
+            raise ValueError('space-to-depth stem input does not match this convolution')
+        wf, wd = _packed_weight_s2d(weight, dt, c), None
+        d = _desc(n, h, w, c, k, (r + 1) // 2, (s + 1) // 2, 1, 0, dt)
+    else:
+        wf, wd = packed_weight(weight, dt, c, need_dx and c == ci)
+        d = _desc(n, h, w, c, k, r, s, stride, pad, dt)
+    L, st, dev = lib(), stream(), x.device
+    y = _empty_nhwc(n, k, d.OH, d.OW, dt, dev)
+    M = n * d.OH * d.OW
+    training = bn.training
+    scale = torch.empty(k, dtype=torch.float32, device=dev)
+    shift = torch.empty(k, dtype=torch.float32, device=dev)
+    mean = invstd = stats = run = None
+    rows = 0
+    # (the pooled form takes scale / shift from the finalize kernel: one 6 us launch, stem only)
+    atomic_rows = training and BN_INLINE and k <= 2048 and not pooled
+    # a deferred apply needs scale / shift as tensors: the finalize launch stays (over the few rows)
+    inline = atomic_rows and not defer
+    flops = 2.0 * M * k * r * s * min(c, ci)
+    if training:
+        rows = L.saicv_conv2d_stat_rows(ctypes.byref(d))
+        t0 = KernelTimer.begin('igemm_nt')
+        if atomic_rows:
+            rows = _stat_rows(rows)
+            stats = _ZeroPool.take(2 * rows * k, dev).view(2, rows, k)
+            check(L.saicv_conv2d_fwd_stats(ctypes.byref(d), ptr(x), ptr(wf), ptr(y), ptr(stats[0]), ptr(stats[1]), rows, st),
+                  'conv2d_fwd_stats')
+        else:
+            stats = torch.empty((2, rows, k), dtype=torch.float32, device=dev)
+            check(L.saicv_conv2d_fwd(ctypes.byref(d), ptr(x), ptr(wf), 0, ptr(y), 0, ptr(stats[0]), ptr(stats[1]), st), 'conv2d_fwd')
+        es = x.element_size()
+        xin_px = M if (r == 1 and stride > 1) else n * h * w          # a strided 1x1 reads a quarter of its input
+        KernelTimer.end(t0, 'igemm_nt', flops, float(xin_px) * c * es + float(k) * r * s * c * es + float(M) * k * es)
+        mean = torch.empty(k, dtype=torch.float32, device=dev)
+        invstd = torch.empty(k, dtype=torch.float32, device=dev)
+        run = _RunningStats(bn, bn.track_running_stats)
+        if not inline:
+            run.finalize(stats[0], stats[1], rows, k, M, gamma, beta, mean, invstd, scale, shift, st)
+    else:
+        t0 = KernelTimer.begin('igemm_nt')
+        check(L.saicv_conv2d_fwd(ctypes.byref(d), ptr(x), ptr(wf), 0, ptr(y), 0, 0, 0, st), 'conv2d_fwd')
+        KernelTimer.end(t0, 'igemm_nt', flops, 0)
+        check(L.saicv_bn_eval_coeffs(k, ptr(gamma), ptr(beta), ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps),
+                                     ptr(scale), ptr(shift), st), 'bn_eval_coeffs')
+    return _ConvStage(x, y, d, wd, M, st, training, inline, stats, rows, mean, invstd, scale, shift, run, float(bn.eps), in_link, s2d)
+
+
+def _remember(ctx, cs, weight, gamma, beta, stride, pad, relu, has_res, mask_or_idx=None, pool=None, gated_res=False, link=None,
+              applies_gate=False):
+    """Everything ConvBnActFn.backward reads, for every tail of the forward: the saved tensors in the one slot order
+    (x, weight, gamma, y, mask_or_idx, mean, invstd_or_scale) and every ctx attribute."""
+    # eval-mode backward (frozen statistics) is linear, dy = scale * g: `scale` travels in the slot of invstd, the others stay empty
+    last = (mask_or_idx, cs.mean, cs.invstd) if cs.training else (None, None, cs.scale)
+    ctx.save_for_backward(cs.x, weight, gamma, cs.y, *last)
+    ctx.cfg = (stride, pad, relu, has_res, cs.training, cs.d, cs.wd)
+    ctx.in_link, ctx.s2d, ctx.pool, ctx.beta_ref = cs.in_link, cs.s2d, pool, beta
+    ctx.gated_res, ctx.link, ctx.applies_gate = gated_res, link, applies_gate
+
+
+def _pooled_tail(ctx, cs, weight, gamma, beta, stride, pad, pool):
+    """BatchNorm-apply + ReLU + MaxPool2d as one pass over the raw convolution output (the ResNet stem)."""
+    pk, ps, pp = pool
+    y, d = cs.y, cs.d
+    n, k = y.shape[0], y.shape[1]
+    poh, pow_ = (d.OH + 2 * pp - pk) // ps + 1, (d.OW + 2 * pp - pk) // ps + 1
+    zp = _empty_nhwc(n, k, poh, pow_, y.dtype, y.device)
+    idx = torch.empty((n, poh, pow_, k), dtype=torch.uint8, device=y.device)
+    t0 = KernelTimer.begin('bn_act_fwd')
+    check(lib().saicv_bn_relu_maxpool_fwd(dtype_code(y.dtype), ptr(y), ptr(cs.scale), ptr(cs.shift), ptr(zp), ptr(idx), n, d.OH, d.OW,
+                                          k, poh, pow_, pk, ps, pp, cs.st), 'bn_relu_maxpool_fwd')
+    es = y.element_size()
+    KernelTimer.end(t0, 'bn_act_fwd', 0, float(cs.M) * k * es + float(n) * poh * pow_ * k * (es + 1))
+    _remember(ctx, cs, weight, gamma, beta, stride, pad, True, False, idx, (pk, ps, pp, poh, pow_, cs.scale, cs.shift))
+    return zp
+
+
+def _apply_tail(ctx, cs, weight, gamma, beta, stride, pad, relu, residual, want_skip):
+    """BatchNorm-apply [+ residual] [+ ReLU] -> z, by the kernel that fits: bn_act_fwd_join when the residual arrives as a raw
+    shortcut convolution + its coefficients, bn_act_fwd_stats when this node's statistics are finalised inline, else bn_act_fwd."""
+    res_gate_ok = bool(residual is not None and getattr(residual, '_saicv_gate_ok', False))
+    res_affine = getattr(residual, '_saicv_deferred', None) if residual is not None else None
+    y, M, run = cs.y, cs.M, cs.run
+    dt, dev = y.dtype, y.device
+    n, k, oh, ow = y.shape
+    if residual is not None:
+        res_in = residual
+        residual = _nhwc(residual, dt)
+        if res_affine is not None and (residual is not res_in or residual.shape != y.shape):
+            # not the tensor the coefficients were made for (a layout / dtype change in between): apply them here
+            residual = (residual.float() * res_affine[0].view(1, -1, 1, 1) + res_affine[1].view(1, -1, 1, 1)).to(dt)
+            residual = _nhwc(residual)
+            res_affine = None
+    z = _empty_nhwc(n, k, oh, ow, dt, dev)
+    # backward needs only the sign of z: one byte per 16-byte chunk instead of re-reading z twice
+    mask = (torch.empty(M * k // _lib.epc(dt), dtype=torch.uint8, device=dev)
+            if (relu and cs.training and any(ctx.needs_input_grad)) else None)
+    L, st = lib(), cs.st
+    t0 = KernelTimer.begin('bn_act_fwd')
+    if res_affine is not None:
+        # the shortcut arrives as a raw convolution output + its BatchNorm coefficients: applied on the fly.  This node's own
+        # coefficients come as tensors or, inline, out of the statistics rows (with everything the finalize kernel does)
+        if cs.inline:
+            own = (0, 0, ptr(cs.stats[0]), ptr(cs.stats[1]), cs.rows)
+            upd = (run.mean, run.var, run.momentum, run.eps, run.nbt, ptr(cs.mean), ptr(cs.invstd))
+        else:
+            own = (ptr(cs.scale), ptr(cs.shift), 0, 0, 0)
+            upd = (0, 0, 0.0, cs.eps, 0, 0, 0)
+        check(L.saicv_bn_act_fwd_join(dtype_code(dt), ptr(y), ptr(residual), ptr(res_affine[0]), ptr(res_affine[1]), ptr(z), *own,
+                                      float(M), ptr(gamma), ptr(beta), *upd, M, k, int(relu), ptr(mask), st), 'bn_act_fwd_join')
+    elif cs.inline:
+        # the kernel derives mean / invstd / scale / shift from the few statistics rows itself (and updates the running
+        # statistics and num_batches_tracked): no finalize launch between the convolution and this one
+        check(L.saicv_bn_act_fwd_stats(dtype_code(dt), ptr(y), ptr(residual), ptr(z), ptr(cs.stats[0]), ptr(cs.stats[1]), cs.rows,
+                                       float(M), ptr(gamma), ptr(beta), run.mean, run.var, run.momentum, run.eps, run.nbt,
+                                       ptr(cs.mean), ptr(cs.invstd), M, k, int(relu), ptr(mask), st), 'bn_act_fwd_stats')
+    else:
+        check(L.saicv_bn_act_fwd(dtype_code(dt), ptr(y), ptr(residual), ptr(z), ptr(cs.scale), ptr(cs.shift), M, k, int(relu),
+                                 ptr(mask), st), 'bn_act_fwd')
+    KernelTimer.end(t0, 'bn_act_fwd', 0, float(M) * k * y.element_size() * (3 if residual is not None else 2))
+    # the shortcut gradient may come back as (gradient, gate) only from nodes that apply gates: the alias of want_skip
+    # (its gradient joins in this node's dgrad epilogue) and BatchNorm nodes without a ReLU of their own
+    gated_res = bool(BN_FUSE and res_gate_ok and mask is not None and ctx.needs_input_grad[4] and residual.shape == z.shape)
+    # conv_bn_act() below hangs link / applies_gate on the OUTPUT tensors (the objects autograd hands back, not the ones made here)
+    link = _BnLink(y, mask, cs.mean, cs.invstd) if (BN_FUSE and mask is not None) else None
+    _remember(ctx, cs, weight, gamma, beta, stride, pad, bool(relu), residual is not None, mask, None, gated_res, link,
+              bool(BN_FUSE and cs.training and not relu))
+    return (z, cs.x) if want_skip else z
+
+
+def _bn_act_backward(ctx, st, dz, dz_is_given, gate_in, relu, has_res, gamma, y, mask, mean, invstd):
+    """dz -> (dy, dres, dgamma, dbeta) behind the BatchNorm-apply [+ residual] [+ ReLU] of the apply tail.  dz_is_given: dz is
+    the tensor autograd handed over, not a re-laid-out or cast copy.  gate_in: a ReLU mask that still has to be applied to dz."""
+    L = lib()
+    dt, dev = y.dtype, y.device
+    n, k, oh, ow = y.shape
+    M = n * oh * ow
+    if gate_in is not None:
+        if relu:
+            raise RuntimeError('a gated shortcut gradient reached a BatchNorm node with its own ReLU')
+        relu, mask = True, gate_in      # same [M][C] coordinates: the tail's mask gates this node's dz
+    dy = _empty_nhwc(n, k, oh, ow, dt, dev)
+    dres = None
+    if has_res and ctx.needs_input_grad[4]:
+        if ctx.gated_res and dz_is_given:
+            # the masked copy g = dz * [z > 0] is not written: the consumer gets dz and the mask
+            dres = dz
+            dres._saicv_gate = mask
+            dres._saicv_gate_version = dres._version
+            _GateLedger.hand_out()
+        else:
+            dres = _empty_nhwc(n, k, oh, ow, dt, dev)
+    dres_out = dres if (dres is not None and dres is not dz) else None
+    dgamma, dbeta, direct_bn = _bn_grad_buffers(gamma, ctx.beta_ref, k, dev)
+    ws = torch.empty(L.saicv_bn_bwd_ws_floats(M, k, dtype_code(dt)), dtype=torch.float32, device=dev)
+    link = ctx.link
+    # dz IS the tensor that data gradient wrote (same memory, never written since): with another consumer of z autograd
+    # hands over a sum in a different tensor and the three-pass form runs
+    fused_reduce = (link is not None and link.part is not None and link.dx is not None and gate_in is None
+                    and dz.data_ptr() == link.dx.data_ptr() and dz.shape == link.dx.shape and dz._version == link.dx_version)
+    t0 = KernelTimer.begin('bn_act_bwd')
+    if fused_reduce and link.inline:
+        # ... as a few atomically accumulated rows: coefficients, dgamma and dbeta come out of the one streaming kernel
+        check(L.saicv_bn_act_bwd_inline(dtype_code(dt), ptr(dz), ptr(mask), ptr(y), ptr(gamma), ptr(mean), ptr(invstd),
+                                        ptr(link.part[0]), ptr(link.part[1]), link.rows, ptr(dy), ptr(dres_out), ptr(dgamma),
+                                        ptr(dbeta), M, k, int(relu), int(direct_bn), st), 'bn_act_bwd_inline')
+    elif fused_reduce:
+        # the data gradient that wrote dz also left the partial sums of this reduction (no pass over dz and y here)
+        check(L.saicv_bn_act_bwd_from_partials(dtype_code(dt), ptr(dz), ptr(mask), ptr(y), ptr(gamma), ptr(mean), ptr(invstd),
+                                               ptr(link.part[0]), ptr(link.part[1]), link.rows, ptr(dy), ptr(dres_out), ptr(dgamma),
+                                               ptr(dbeta), M, k, int(relu), int(direct_bn), ptr(ws), st), 'bn_act_bwd_from_partials')
+    else:
+        check(L.saicv_bn_act_bwd(dtype_code(dt), ptr(dz), 0, ptr(mask), ptr(y), ptr(gamma), ptr(mean), ptr(invstd),
+                                 ptr(dy), ptr(dres_out), ptr(dgamma), ptr(dbeta), M, k, int(relu), int(direct_bn),
+                                 ptr(ws), st), 'bn_act_bwd')
+    if link is not None:
+        link.part = link.dx = None
+    # streaming passes over (dz, y) (+ the 1-bit ReLU mask): reduction unless fused away, then apply; dy (and dres) written
+    KernelTimer.end(t0, 'bn_act_bwd', 0, float(M) * k * y.element_size() *
+                    ((1 if fused_reduce else 2) * (2 + (1.0 / 16 if relu else 0)) + (2 if dres_out is not None else 1)))
+    return (dy, dres, None, None) if direct_bn else (dy, dres, dgamma, dbeta)
+
+
+def _dgrad_fuse(d, in_link, addend, gate, dev):
+    """The epilogue of a fused data gradient (_lib.DgradFuse): + addend [* gate], and / or the backward partial sums of the
+    BatchNorm(+ReLU) node behind `in_link`, parked on the link for that node's backward."""
+    fuse = _lib.DgradFuse()
+    fuse.addend, fuse.addend_gate = ptr(addend), ptr(gate)
+    if in_link is not None:
+        c = d.C
+        rows = lib().saicv_conv2d_dgrad_stat_rows(ctypes.byref(d))
+        in_link.inline = BN_INLINE and c <= 2048
+        if in_link.inline:
+            rows = _stat_rows(rows)
+            part = _ZeroPool.take(2 * rows * c, dev).view(2, rows, c)
+            fuse.part_rows = rows
+        else:
+            part = torch.empty((2, rows, c), dtype=torch.float32, device=dev)
+        fuse.bn_y, fuse.bn_mask = ptr(in_link.y), ptr(in_link.mask)
+        fuse.bn_mean, fuse.bn_invstd = ptr(in_link.mean), ptr(in_link.invstd)
+        fuse.part_g, fuse.part_gx = ptr(part[0]), ptr(part[1])
+        in_link.part, in_link.rows = part, rows
+    return fuse
+
+
+def _pooled_bn_backward(ctx, st, dz, gamma, y, idx, mean, invstd):
+    """The pooled stem block's half of backward: pooled gradient -> (max-pool backward + ReLU gate + BatchNorm backward in two
+    passes over y) -> (dy at full resolution, no dres, dgamma, dbeta); ConvBnActFn.backward goes on from dy as behind its own kernels."""
+    pk, ps, pp, poh, pow_, scale, shift = ctx.pool
+    L = lib()
+    dt, dev = y.dtype, y.device
+    n, k, oh, ow = y.shape
+    dy = _empty_nhwc(n, k, oh, ow, dt, dev)
+    dgamma, dbeta, direct_bn = _bn_grad_buffers(gamma, ctx.beta_ref, k, dev)
+    ws = torch.empty(L.saicv_bn_relu_maxpool_bwd_ws_floats(k), dtype=torch.float32, device=dev)
+    t0 = KernelTimer.begin('bn_act_bwd')
+    check(L.saicv_bn_relu_maxpool_bwd(dtype_code(dt), ptr(dz), ptr(idx), ptr(y), ptr(gamma), ptr(mean), ptr(invstd), ptr(scale),
+                                      ptr(shift), ptr(dy), ptr(dgamma), ptr(dbeta), int(direct_bn), ptr(ws), n, oh, ow, k, poh, pow_,
+                                      pk, ps, pp, st), 'bn_relu_maxpool_bwd')
+    es = y.element_size()
+    KernelTimer.end(t0, 'bn_act_bwd', 0, 3.0 * n * oh * ow * k * es + 2.0 * n * poh * pow_ * k * (es + 1))  # y twice + dy; dout + idx twice
+    return (dy, None, None, None) if direct_bn else (dy, None, dgamma, dbeta)
+
+
 class ConvBnActFn(torch.autograd.Function):
     """conv -> [BatchNorm2d (train: batch stats, eval: running stats)] -> [+residual] -> [ReLU].
 
     Mirrors reference ConvBnActBlock (classification/backbones/resnet.py:19-48) plus the
     residual tail of BasicBlock / Bottleneck (:94-95, :152-153)."""
+
+    # return channel of a deferred forward to conv_bn_act (a tensor attribute set inside forward does not survive apply(), and
+    # under no_grad there is no grad_fn to carry it): forward pushes (scale, shift) right before it returns, conv_bn_act pops
+    _deferred = []
 
     @staticmethod
     def forward(ctx, x, weight, gamma, beta, residual, bn, stride, pad, relu, want_skip=False, pool=None, defer=False):
@@ -544,174 +869,19 @@ class ConvBnActFn(torch.autograd.Function):
         want_skip: also return the (NHWC) input as a second output.  A residual block routes its shortcut
         through that alias, so the shortcut's gradient reaches THIS node's backward and is added in the
         dgrad kernel's epilogue instead of by a separate elementwise add."""
-        require_gpu(x, weight)
-        in_link = getattr(x, '_saicv_bn', None) if BN_FUSE else None
-        xin = x
-        res_gate_ok = bool(residual is not None and getattr(residual, '_saicv_gate_ok', False))
-        res_affine = getattr(residual, '_saicv_deferred', None) if residual is not None else None
         if defer and (residual is not None or relu or want_skip or pool is not None):
             raise ValueError('a deferred BatchNorm-apply belongs to a plain convolution + BatchNorm shortcut')
-        x = _nhwc(x)
-        dt = x.dtype
-        n, c, h, w = x.shape
-        k, ci, r, s = weight.shape
-        if c < ci:
-            raise ValueError(f'input has {c} channels, weight expects {ci}')
-        need_dx = ctx.needs_input_grad[0]
-        # this conv's data gradient IS the dz of the BatchNorm(+ReLU) node that produced x (when x has no other consumer):
-        # it can leave that node's backward partial sums behind
-        ctx.in_link = in_link if (in_link is not None and x is xin and need_dx and c == ci and in_link.y.shape == x.shape
-                                  and in_link.y.dtype == dt) else None
-        s2d = getattr(xin, '_saicv_s2d', None)
-        if s2d is not None:
-            # stride-2 stem on the space-to-depth image (pack_stem_input): a stride-1 convolution with (R+1)/2 taps
-            if need_dx or (s2d[0], s2d[3], s2d[4]) != (ci, r, pad) or stride != 2 or r != s:
-                raise ValueError('space-to-depth stem input does not match this convolution')
-            wf, wd = _packed_weight_s2d(weight, dt, c), None
-            d = _desc(n, h, w, c, k, (r + 1) // 2, (s + 1) // 2, 1, 0, dt)
-        else:
-            wf, wd = packed_weight(weight, dt, c, need_dx and c == ci)
-            d = _desc(n, h, w, c, k, r, s, stride, pad, dt)
-        ctx.s2d = s2d
-        L = lib()
-        st = stream()
-        dev = x.device
-        y = _empty_nhwc(n, k, d.OH, d.OW, dt, dev)
-        M = n * d.OH * d.OW
-        training = bn.training
-        scale = torch.empty(k, dtype=torch.float32, device=dev)
-        shift = torch.empty(k, dtype=torch.float32, device=dev)
-        mean = invstd = None
         if pool is not None and (residual is not None or not relu or want_skip):
             raise ValueError('the fused max-pool follows a plain conv -> BatchNorm -> ReLU block')
-        # (the pooled form takes scale / shift from the finalize kernel: one 6 us launch, stem only)
-        inline = training and BN_INLINE and k <= 2048 and pool is None
-        atomic_rows = inline
-        if defer:
-            inline = False                   # scale / shift must exist as tensors: the finalize launch stays (over the few rows)
-        if training:
-            rows = L.saicv_conv2d_stat_rows(ctypes.byref(d))
-            t0 = KernelTimer.begin('igemm_nt')
-            if atomic_rows:
-                rows = _stat_rows(rows)
-                stats = _ZeroPool.take(2 * rows * k, dev).view(2, rows, k)
-                check(L.saicv_conv2d_fwd_stats(ctypes.byref(d), ptr(x), ptr(wf), ptr(y), ptr(stats[0]), ptr(stats[1]), rows, st),
-                      'conv2d_fwd_stats')
-            else:
-                stats = torch.empty((2, rows, k), dtype=torch.float32, device=dev)
-                check(L.saicv_conv2d_fwd(ctypes.byref(d), ptr(x), ptr(wf), 0, ptr(y), 0, ptr(stats[0]),
-                                         ptr(stats[1]), st), 'conv2d_fwd')
-            es = x.element_size()
-            xin_px = M if (r == 1 and stride > 1) else n * h * w          # a strided 1x1 reads a quarter of its input
-            KernelTimer.end(t0, 'igemm_nt', 2.0 * M * k * r * s * min(c, ci),
-                            float(xin_px) * c * es + float(k) * r * s * c * es + float(M) * k * es)
-            mean = torch.empty(k, dtype=torch.float32, device=dev)
-            invstd = torch.empty(k, dtype=torch.float32, device=dev)
-            if bn.momentum is None:
-                raise NotImplementedError('BatchNorm2d(momentum=None) is not supported')
-            track = bn.track_running_stats and bn.running_mean is not None
-            nbt = bn.num_batches_tracked if (track and bn.num_batches_tracked is not None) else None
-            if not inline:
-                ws = torch.empty(L.saicv_bn_ws_floats(k), dtype=torch.float32, device=dev)
-                check(L.saicv_bn_finalize_fwd(ptr(stats[0]), ptr(stats[1]), rows, k, float(M), ptr(gamma),
-                                              ptr(beta), ptr(bn.running_mean) if track else 0,
-                                              ptr(bn.running_var) if track else 0, float(bn.momentum),
-                                              float(bn.eps), ptr(mean), ptr(invstd), ptr(scale), ptr(shift),
-                                              ptr(ws), ptr(nbt), st), 'bn_finalize_fwd')      # also num_batches_tracked += 1
-        else:
-            t0 = KernelTimer.begin('igemm_nt')
-            check(L.saicv_conv2d_fwd(ctypes.byref(d), ptr(x), ptr(wf), 0, ptr(y), 0, 0, 0, st), 'conv2d_fwd')
-            KernelTimer.end(t0, 'igemm_nt', 2.0 * M * k * r * s * min(c, ci), 0)
-            check(L.saicv_bn_eval_coeffs(k, ptr(gamma), ptr(beta), ptr(bn.running_mean),
-                                         ptr(bn.running_var), float(bn.eps), ptr(scale), ptr(shift), st),
-                  'bn_eval_coeffs')
+        cs = _conv_stage(x, weight, gamma, beta, bn, stride, pad, ctx.needs_input_grad[0], pool is not None, defer)
         if pool is not None:
-            pk, ps, pp = pool
-            poh, pow_ = (d.OH + 2 * pp - pk) // ps + 1, (d.OW + 2 * pp - pk) // ps + 1
-            zp = _empty_nhwc(n, k, poh, pow_, dt, dev)
-            idx = torch.empty((n, poh, pow_, k), dtype=torch.uint8, device=dev)
-            t0 = KernelTimer.begin('bn_act_fwd')
-            check(L.saicv_bn_relu_maxpool_fwd(dtype_code(dt), ptr(y), ptr(scale), ptr(shift), ptr(zp), ptr(idx), n, d.OH, d.OW, k,
-                                              poh, pow_, pk, ps, pp, st), 'bn_relu_maxpool_fwd')
-            es = y.element_size()
-            KernelTimer.end(t0, 'bn_act_fwd', 0, float(M) * k * es + float(n) * poh * pow_ * k * (es + 1))
-            if training:
-                ctx.save_for_backward(x, weight, gamma, y, idx, mean, invstd)
-            else:
-                ctx.save_for_backward(x, weight, gamma, y, None, None, scale)
-            ctx.cfg = (stride, pad, True, False, training, d, wd)
-            ctx.pool = (pk, ps, pp, poh, pow_, scale, shift)
-            ctx.beta_ref = beta
-            ctx.gated_res = False
-            ctx.link = None
-            ctx.applies_gate = False
-            return zp
-        ctx.pool = None
+            return _pooled_tail(ctx, cs, weight, gamma, beta, stride, pad, pool)
         if defer:
-            ConvBnActFn._deferred = (scale, shift)
-            if training:
-                ctx.save_for_backward(x, weight, gamma, y, None, mean, invstd)
-            else:
-                ctx.save_for_backward(x, weight, gamma, y, None, None, scale)
-            ctx.cfg = (stride, pad, False, False, training, d, wd)
-            ctx.beta_ref = beta
-            ctx.gated_res = False
-            ctx.link = None
-            ctx.applies_gate = bool(BN_FUSE and training)
-            return y
-        if residual is not None:
-            res_in = residual
-            residual = _nhwc(residual)
-            if residual.dtype != dt:
-                residual = residual.to(dt)
-            if res_affine is not None and (residual is not res_in or residual.shape != y.shape):
-                # not the tensor the coefficients were made for (a layout / dtype change in between): apply them here
-                residual = (residual.float() * res_affine[0].view(1, -1, 1, 1) + res_affine[1].view(1, -1, 1, 1)).to(dt)
-                residual = _nhwc(residual)
-                res_affine = None
-        z = _empty_nhwc(n, k, d.OH, d.OW, dt, dev)
-        # backward needs only the sign of z: one byte per 16-byte chunk instead of re-reading z twice
-        mask = (torch.empty(M * k // _lib.epc(dt), dtype=torch.uint8, device=dev)
-                if (relu and training and any(ctx.needs_input_grad)) else None)
-        t0 = KernelTimer.begin('bn_act_fwd')
-        if res_affine is not None:
-            # the shortcut arrives as a raw convolution output + its BatchNorm coefficients: applied on the fly
-            check(L.saicv_bn_act_fwd_join(dtype_code(dt), ptr(y), ptr(residual), ptr(res_affine[0]), ptr(res_affine[1]), ptr(z),
-                                          0 if inline else ptr(scale), 0 if inline else ptr(shift),
-                                          ptr(stats[0]) if inline else 0, ptr(stats[1]) if inline else 0, rows if inline else 0,
-                                          float(M), ptr(gamma), ptr(beta), ptr(bn.running_mean) if (inline and track) else 0,
-                                          ptr(bn.running_var) if (inline and track) else 0,
-                                          float(bn.momentum) if inline else 0.0, float(bn.eps), ptr(nbt) if inline else 0,
-                                          ptr(mean) if inline else 0, ptr(invstd) if inline else 0, M, k, int(relu), ptr(mask), st),
-                  'bn_act_fwd_join')
-        elif inline:
-            # the kernel derives mean / invstd / scale / shift from the few statistics rows itself (and updates the running
-            # statistics and num_batches_tracked): no finalize launch between the convolution and this one
-            check(L.saicv_bn_act_fwd_stats(dtype_code(dt), ptr(y), ptr(residual), ptr(z), ptr(stats[0]), ptr(stats[1]), rows,
-                                           float(M), ptr(gamma), ptr(beta), ptr(bn.running_mean) if track else 0,
-                                           ptr(bn.running_var) if track else 0, float(bn.momentum), float(bn.eps), ptr(nbt),
-                                           ptr(mean), ptr(invstd), M, k, int(relu), ptr(mask), st), 'bn_act_fwd_stats')
-        else:
-            check(L.saicv_bn_act_fwd(dtype_code(dt), ptr(y), ptr(residual), ptr(z), ptr(scale), ptr(shift), M,
-                                     k, int(relu), ptr(mask), st), 'bn_act_fwd')
-        KernelTimer.end(t0, 'bn_act_fwd', 0, float(M) * k * y.element_size() * (3 if residual is not None else 2))
-        if training:
-            ctx.save_for_backward(x, weight, gamma, y, mask, mean, invstd)
-        else:
-            # eval-mode backward (frozen statistics) is linear: dy = scale * g
-            ctx.save_for_backward(x, weight, gamma, y, None, None, scale)
-        ctx.cfg = (stride, pad, bool(relu), residual is not None, training, d, wd)
-        ctx.beta_ref = beta
-        # the shortcut gradient may come back as (gradient, gate) only from nodes that apply gates: the alias below
-        # (its gradient joins in this node's dgrad epilogue) and BatchNorm nodes without a ReLU of their own
-        ctx.gated_res = bool(BN_FUSE and res_gate_ok and mask is not None and ctx.needs_input_grad[4]
-                             and residual.shape == z.shape)
-        # conv_bn_act() below hangs these on the OUTPUT tensors (the objects autograd hands back, not the ones made here)
-        ctx.link = _BnLink(y, mask, mean, invstd) if (BN_FUSE and mask is not None) else None
-        ctx.applies_gate = bool(BN_FUSE and training and not relu)
-        if want_skip:
-            return z, x
-        return z
+            # the raw output; its gradient is the normalised shortcut's and may arrive gated (no ReLU of its own)
+            _remember(ctx, cs, weight, gamma, beta, stride, pad, False, False, applies_gate=bool(BN_FUSE and cs.training))
+            ConvBnActFn._deferred.append((cs.scale, cs.shift))
+            return cs.y
+        return _apply_tail(ctx, cs, weight, gamma, beta, stride, pad, relu, residual, want_skip)
 
     @staticmethod
     def backward(ctx, dz, dskip=None):
@@ -719,111 +889,30 @@ class ConvBnActFn(torch.autograd.Function):
         stride, pad, relu, has_res, training, d, wd = ctx.cfg
         if not training:
             raise NotImplementedError('backward through eval-mode BatchNorm is not implemented')
-        L = lib()
-        st = stream()
-        dt = y.dtype
-        dev = y.device
+        dt, st = y.dtype, stream()
         gate_in = _take_gate(dz)          # dz is a shortcut gradient still waiting for the ReLU mask of the block's tail
         dz0 = dz
-        dz = _nhwc(dz)
-        if dz.dtype != dt:
-            dz = dz.to(dt)
+        dz = _nhwc(dz, dt)
+        if ctx.pool is not None:
+            dy, dres, dgamma, dbeta = _pooled_bn_backward(ctx, st, dz, gamma, y, mask, mean, invstd)
+        else:
+            dy, dres, dgamma, dbeta = _bn_act_backward(ctx, st, dz, dz is dz0, gate_in, relu, has_res, gamma, y, mask, mean, invstd)
         n, k, oh, ow = y.shape
         M = n * oh * ow
-        if ctx.pool is not None:
-            return ConvBnActFn._backward_pooled(ctx, dz, x, weight, gamma, y, mask, mean, invstd)
-        if gate_in is not None:
-            if relu:
-                raise RuntimeError('a gated shortcut gradient reached a BatchNorm node with its own ReLU')
-            relu, mask = True, gate_in      # same [M][C] coordinates: the tail's mask gates this node's dz
-        dy = _empty_nhwc(n, k, oh, ow, dt, dev)
-        dres = None
-        if has_res and ctx.needs_input_grad[4]:
-            if ctx.gated_res and dz is dz0:
-                # the masked copy g = dz * [z > 0] is not written: the consumer gets dz and the mask
-                dres = dz
-                dres._saicv_gate = mask
-                dres._saicv_gate_version = dres._version
-                _GateLedger.hand_out()
-            else:
-                dres = _empty_nhwc(n, k, oh, ow, dt, dev)
-        dres_out = dres if (dres is not None and dres is not dz) else None
-        beta = ctx.beta_ref
-        gg, gb = _arena_grad(gamma), _arena_grad(beta)
-        direct_bn = gg is not None and gb is not None
-        if direct_bn:
-            dgamma, dbeta = gg, gb
-        else:
-            dgamma = torch.empty(k, dtype=torch.float32, device=dev)
-            dbeta = torch.empty(k, dtype=torch.float32, device=dev)
-        ws = torch.empty(L.saicv_bn_bwd_ws_floats(M, k, dtype_code(dt)), dtype=torch.float32, device=dev)
-        link = ctx.link
-        # dz IS the tensor that data gradient wrote (same memory, never written since): with another consumer of z autograd
-        # hands over a sum in a different tensor and the three-pass form runs
-        fused_reduce = (link is not None and link.part is not None and link.dx is not None and gate_in is None
-                        and dz.data_ptr() == link.dx.data_ptr() and dz.shape == link.dx.shape
-                        and dz._version == link.dx_version)
-        t0 = KernelTimer.begin('bn_act_bwd')
-        if fused_reduce and link.inline:
-            # ... as a few atomically accumulated rows: coefficients, dgamma and dbeta come out of the one streaming kernel
-            check(L.saicv_bn_act_bwd_inline(dtype_code(dt), ptr(dz), ptr(mask), ptr(y), ptr(gamma), ptr(mean), ptr(invstd),
-                                            ptr(link.part[0]), ptr(link.part[1]), link.rows, ptr(dy), ptr(dres_out), ptr(dgamma),
-                                            ptr(dbeta), M, k, int(relu), int(direct_bn), st), 'bn_act_bwd_inline')
-        elif fused_reduce:
-            # the data gradient that wrote dz also left the partial sums of this reduction (no pass over dz and y here)
-            check(L.saicv_bn_act_bwd_from_partials(dtype_code(dt), ptr(dz), ptr(mask), ptr(y), ptr(gamma), ptr(mean),
-                                                   ptr(invstd), ptr(link.part[0]), ptr(link.part[1]), link.rows, ptr(dy),
-                                                   ptr(dres_out), ptr(dgamma), ptr(dbeta), M, k, int(relu), int(direct_bn),
-                                                   ptr(ws), st), 'bn_act_bwd_from_partials')
-        else:
-            check(L.saicv_bn_act_bwd(dtype_code(dt), ptr(dz), 0, ptr(mask), ptr(y), ptr(gamma), ptr(mean), ptr(invstd),
-                                     ptr(dy), ptr(dres_out), ptr(dgamma), ptr(dbeta), M, k, int(relu), int(direct_bn),
-                                     ptr(ws), st), 'bn_act_bwd')
-        if link is not None:
-            link.part = link.dx = None
-        if direct_bn:
-            dgamma = dbeta = None
-        # streaming passes over (dz, y) (+ the 1-bit ReLU mask): reduction unless fused away, then apply; dy (and dres) written
-        KernelTimer.end(t0, 'bn_act_bwd', 0, float(M) * k * y.element_size() *
-                        ((1 if fused_reduce else 2) * (2 + (1.0 / 16 if relu else 0)) + (2 if dres_out is not None else 1)))
         c = x.shape[1]
         flops = 2.0 * M * k * weight.shape[2] * weight.shape[3] * min(c, weight.shape[1])
-        dx = None
+        dx = dwt = None
         if ctx.needs_input_grad[0]:
-            if wd is None:
-                _, wd = packed_weight(weight, dt, c, True)
-            dx = _empty_nhwc(n, c, x.shape[2], x.shape[3], dt, dev)
             t0 = KernelTimer.begin('igemm_nt')
             gate = None
             if dskip is not None:           # gradient of the shortcut alias joins in the dgrad epilogue
                 gate = _take_gate(dskip)
-                dskip = _nhwc(dskip)
-                if dskip.dtype != dt:
-                    dskip = dskip.to(dt)
+                dskip = _nhwc(dskip, dt)
             in_link = ctx.in_link
-            if gate is not None or in_link is not None:
-                fuse = _lib.DgradFuse()
-                fuse.addend, fuse.addend_gate = ptr(dskip), ptr(gate)
-                if in_link is not None:
-                    rows = L.saicv_conv2d_dgrad_stat_rows(ctypes.byref(d))
-                    in_link.inline = BN_INLINE and c <= 2048
-                    if in_link.inline:
-                        rows = _stat_rows(rows)
-                        part = _ZeroPool.take(2 * rows * c, dev).view(2, rows, c)
-                        fuse.part_rows = rows
-                    else:
-                        part = torch.empty((2, rows, c), dtype=torch.float32, device=dev)
-                    fuse.bn_y, fuse.bn_mask = ptr(in_link.y), ptr(in_link.mask)
-                    fuse.bn_mean, fuse.bn_invstd = ptr(in_link.mean), ptr(in_link.invstd)
-                    fuse.part_g, fuse.part_gx = ptr(part[0]), ptr(part[1])
-                    in_link.part, in_link.rows, in_link.dx, in_link.dx_version = part, rows, dx, dx._version
-                check(L.saicv_conv2d_dgrad_fused(ctypes.byref(d), ptr(dy), ptr(wd), ctypes.byref(fuse), ptr(dx), st),
-                      'conv2d_dgrad_fused')
-            elif dskip is not None:
-                check(L.saicv_conv2d_dgrad_add(ctypes.byref(d), ptr(dy), ptr(wd), ptr(dskip), ptr(dx), st),
-                      'conv2d_dgrad_add')
-            else:
-                check(L.saicv_conv2d_dgrad(ctypes.byref(d), ptr(dy), ptr(wd), ptr(dx), st), 'conv2d_dgrad')
+            fuse = _dgrad_fuse(d, in_link, dskip, gate, y.device) if (gate is not None or in_link is not None) else None
+            dx = _conv_data_grad(d, dy, weight, wd, x.shape, dt, st, fuse, dskip)
+            if in_link is not None:
+                in_link.dx, in_link.dx_version = dx, dx._version
             es = dy.element_size()
             px = float(n) * x.shape[2] * x.shape[3] * c          # elements of dx (and of every epilogue tensor)
             nbytes = float(M) * k * es + float(k) * d.R * d.S * c * es + px * es
@@ -831,72 +920,13 @@ class ConvBnActFn(torch.autograd.Function):
                 nbytes += px * es + (px / 8 if gate is not None else 0)
             if in_link is not None:
                 nbytes += px * es + px / 8
-            KernelTimer.end(t0, 'igemm_nt', flops, nbytes)
-        dwt = None
+            KernelTimer.end(t0, 'igemm_nt', flops, nbytes if ctx.pool is None else 0)
         if ctx.needs_input_grad[1]:
-            gw = _arena_grad(weight)
-            direct = (gw is not None and c == weight.shape[1] and
-                      weight.is_contiguous(memory_format=torch.channels_last))
-            # KRSC fp32 gradient: straight into the arena (atomics accumulate), else a temporary
-            dw = gw if direct else torch.zeros((k, d.R, d.S, c), dtype=torch.float32, device=dev)
             t0 = KernelTimer.begin('igemm_tn')
-            check(L.saicv_conv2d_wgrad(ctypes.byref(d), ptr(dy), ptr(x), ptr(dw), st), 'conv2d_wgrad')
+            dwt = _conv_weight_grad(d, dy, x, weight, st, ctx.s2d)
             KernelTimer.end(t0, 'igemm_tn', flops, 0)
-            if not direct:
-                dwt = _weight_grad_s2d(dw, weight, c, gw) if ctx.s2d is not None else _weight_grad(dw, weight, c)
         return (dx, dwt, dgamma if ctx.needs_input_grad[2] else None,
                 dbeta if ctx.needs_input_grad[3] else None, dres, None, None, None, None, None, None, None)
-
-
-def _conv_bn_act_backward_pooled(ctx, dz, x, weight, gamma, y, idx, mean, invstd):
-    """backward of the pooled stem block: pooled gradient -> (max-pool backward + ReLU gate + BatchNorm backward in two passes over
-    y) -> dy at full resolution -> [data gradient] + weight gradient, as ConvBnActFn.backward does behind its BatchNorm kernels."""
-    stride, pad, _, _, _, d, wd = ctx.cfg
-    pk, ps, pp, poh, pow_, scale, shift = ctx.pool
-    L, st = lib(), stream()
-    dt, dev = y.dtype, y.device
-    n, k, oh, ow = y.shape
-    M = n * oh * ow
-    dy = _empty_nhwc(n, k, oh, ow, dt, dev)
-    beta = ctx.beta_ref
-    gg, gb = _arena_grad(gamma), _arena_grad(beta)
-    direct_bn = gg is not None and gb is not None
-    dgamma = gg if direct_bn else torch.empty(k, dtype=torch.float32, device=dev)
-    dbeta = gb if direct_bn else torch.empty(k, dtype=torch.float32, device=dev)
-    ws = torch.empty(L.saicv_bn_relu_maxpool_bwd_ws_floats(k), dtype=torch.float32, device=dev)
-    t0 = KernelTimer.begin('bn_act_bwd')
-    check(L.saicv_bn_relu_maxpool_bwd(dtype_code(dt), ptr(dz), ptr(idx), ptr(y), ptr(gamma), ptr(mean), ptr(invstd), ptr(scale),
-                                      ptr(shift), ptr(dy), ptr(dgamma), ptr(dbeta), int(direct_bn), ptr(ws), n, oh, ow, k, poh, pow_,
-                                      pk, ps, pp, st), 'bn_relu_maxpool_bwd')
-    es = y.element_size()
-    KernelTimer.end(t0, 'bn_act_bwd', 0, 3.0 * M * k * es + 2.0 * n * poh * pow_ * k * (es + 1))       # y twice + dy; dout + idx twice
-    if direct_bn:
-        dgamma = dbeta = None
-    c = x.shape[1]
-    flops = 2.0 * M * k * weight.shape[2] * weight.shape[3] * min(c, weight.shape[1])
-    dx = None
-    if ctx.needs_input_grad[0]:
-        if wd is None:
-            _, wd = packed_weight(weight, dt, c, True)
-        dx = _empty_nhwc(n, c, x.shape[2], x.shape[3], dt, dev)
-        t0 = KernelTimer.begin('igemm_nt')
-        check(L.saicv_conv2d_dgrad(ctypes.byref(d), ptr(dy), ptr(wd), ptr(dx), st), 'conv2d_dgrad')
-        KernelTimer.end(t0, 'igemm_nt', flops, 0)
-    dwt = None
-    if ctx.needs_input_grad[1]:
-        gw = _arena_grad(weight)
-        direct = gw is not None and c == weight.shape[1] and weight.is_contiguous(memory_format=torch.channels_last)
-        dw = gw if direct else torch.zeros((k, d.R, d.S, c), dtype=torch.float32, device=dev)
-        t0 = KernelTimer.begin('igemm_tn')
-        check(L.saicv_conv2d_wgrad(ctypes.byref(d), ptr(dy), ptr(x), ptr(dw), st), 'conv2d_wgrad')
-        KernelTimer.end(t0, 'igemm_tn', flops, 0)
-        if not direct:
-            dwt = _weight_grad_s2d(dw, weight, c, gw) if ctx.s2d is not None else _weight_grad(dw, weight, c)
-    return (dx, dwt, dgamma if ctx.needs_input_grad[2] else None, dbeta if ctx.needs_input_grad[3] else None,
-            None, None, None, None, None, None, None, None)
-
-
-ConvBnActFn._backward_pooled = staticmethod(_conv_bn_act_backward_pooled)
 
 
 def conv_bn_act(x, weight, bn, stride, pad, relu, residual=None, want_skip=False, pool=None, defer=False):
@@ -908,9 +938,8 @@ def conv_bn_act(x, weight, bn, stride, pad, relu, residual=None, want_skip=False
     if pool is not None:
         return ConvBnActFn.apply(x, weight, bn.weight, bn.bias, None, bn, stride, pad, relu, False, pool)
     if defer:
-        ConvBnActFn._deferred = None
         out = ConvBnActFn.apply(x, weight, bn.weight, bn.bias, None, bn, stride, pad, False, False, None, True)
-        out._saicv_deferred, ConvBnActFn._deferred = ConvBnActFn._deferred, None
+        out._saicv_deferred = ConvBnActFn._deferred.pop()
         if BN_FUSE and out.grad_fn is not None and getattr(out.grad_fn, 'applies_gate', False):
             out._saicv_gate_ok = True
         return out
@@ -959,65 +988,47 @@ class ConvFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight, bias = ctx.saved_tensors
         d, wd = ctx.cfg
-        L, st = lib(), stream()
-        dt = x.dtype
-        dy = _nhwc(dy)
-        if dy.dtype != dt:
-            dy = dy.to(dt)
+        dt, st = x.dtype, stream()
+        dy = _nhwc(dy, dt)
         n, c, h, w = x.shape
         k = weight.shape[0]
         e = _lib.epc(dt)
+        dx = dwt = db = None
         if k % e:
             # output channels that are not whole 16-byte chunks (RetinaNet's 9 x 4 box offsets, FCOS's 4 + 1 outputs): the
             # backward kernels gather dY by chunks, so dY travels zero-padded to kp channels and the gradients are sliced back
+            # (the padded descriptor keeps the weight gradient out of the arena: _conv_weight_grad)
             kp = (k + e - 1) // e * e
             dyp = torch.zeros((n, kp, d.OH, d.OW), dtype=dt, device=dy.device).contiguous(memory_format=torch.channels_last)
             dyp[:, :k] = dy
             dp = _desc(n, h, w, c, kp, d.R, d.S, d.stride, d.pad, dt)
-            dx = dwt = db = None
             if ctx.needs_input_grad[0]:
-                _, wdp = packed_weight(weight, dt, c, True, kp)
-                dx = _empty_nhwc(n, c, h, w, dt, x.device)
-                check(L.saicv_conv2d_dgrad(ctypes.byref(dp), ptr(dyp), ptr(wdp), ptr(dx), st), 'conv2d_dgrad')
+                dx = _conv_data_grad(dp, dyp, weight, None, x.shape, dt, st)
             if ctx.needs_input_grad[1]:
-                dwp = torch.zeros((kp, d.R, d.S, c), dtype=torch.float32, device=x.device)
-                check(L.saicv_conv2d_wgrad(ctypes.byref(dp), ptr(dyp), ptr(x), ptr(dwp), st), 'conv2d_wgrad')
-                dwt = dwp[:k].permute(0, 3, 1, 2).to(weight.dtype)
+                dwt = _conv_weight_grad(dp, dyp, x, weight, st)[:k].to(weight.dtype)
             if bias is not None and ctx.needs_input_grad[2]:
                 db = dy.float().sum((0, 2, 3)).to(bias.dtype)
             return dx, dwt, db, None, None
         M = n * d.OH * d.OW
         flops = 2.0 * M * k * d.R * d.S * c
-        dx = dwt = db = None
         if ctx.needs_input_grad[0]:
-            if wd is None:
-                _, wd = packed_weight(weight, dt, c, True)
-            dx = _empty_nhwc(n, c, h, w, dt, x.device)
             t0 = KernelTimer.begin('igemm_nt')
-            check(L.saicv_conv2d_dgrad(ctypes.byref(d), ptr(dy), ptr(wd), ptr(dx), st), 'conv2d_dgrad')
+            dx = _conv_data_grad(d, dy, weight, wd, x.shape, dt, st)
             KernelTimer.end(t0, 'igemm_nt', flops, 0)
         want_b = bias is not None and ctx.needs_input_grad[2]
         tb = gb = None
-        bias_done = False
         if want_b:
             gb = _arena_grad(bias)
             tb = gb if gb is not None else torch.zeros(k, dtype=torch.float32, device=x.device)
         if ctx.needs_input_grad[1]:
-            gw = _arena_grad(weight)
-            direct = gw is not None and c == weight.shape[1] and weight.is_contiguous(memory_format=torch.channels_last)
-            dw = gw if direct else torch.zeros((k, d.R, d.S, c), dtype=torch.float32, device=x.device)
             t0 = KernelTimer.begin('igemm_tn')
             # the bias gradient rides along: column sums of the dY tiles the weight-gradient kernel already holds
-            check(L.saicv_conv2d_wgrad_bias(ctypes.byref(d), ptr(dy), ptr(x), ptr(dw), ptr(tb), st), 'conv2d_wgrad')
+            dwt = _conv_weight_grad(d, dy, x, weight, st, None, tb)
             KernelTimer.end(t0, 'igemm_tn', flops, 0)
-            bias_done = want_b
-            if not direct:
-                dwt = _weight_grad(dw, weight, c)
-        if want_b:
-            if not bias_done:                   # no weight gradient wanted: its own pass
-                check(L.saicv_colsum(dtype_code(dt), ptr(dy), M, k, ptr(tb), st), 'colsum')
-            if gb is None:
-                db = tb
+        elif want_b:                            # no weight gradient wanted: its own pass
+            check(lib().saicv_colsum(dtype_code(dt), ptr(dy), M, k, ptr(tb), st), 'colsum')
+        if gb is None:
+            db = tb
         return dx, dwt, db, None, None
 
 
@@ -1061,9 +1072,7 @@ class DepthwiseConvFn(torch.autograd.Function):
         n, h, w, c, oh, ow, k, stride, pad, dilation = ctx.cfg
         L, st = lib(), stream()
         dt = x.dtype
-        dy = _nhwc(dy)
-        if dy.dtype != dt:
-            dy = dy.to(dt)
+        dy = _nhwc(dy, dt)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = _empty_nhwc(n, c, h, w, dt, x.device)
@@ -1181,9 +1190,7 @@ class ScaleAddFn(torch.autograd.Function):
     def backward(ctx, dout):
         y, sf, s = ctx.saved_tensors
         n, c, h, w, dt = ctx.cfg
-        dout = _nhwc(dout)
-        if dout.dtype != dt:
-            dout = dout.to(dt)
+        dout = _nhwc(dout, dt)
         dx = dout if ctx.needs_input_grad[0] else None        # (needs_input_grad[0] is False for x = None)
         if s is None:
             return dx, (dout if ctx.needs_input_grad[1] else None), None
@@ -1244,19 +1251,12 @@ class BatchNorm2dFn(torch.autograd.Function):
         shift = torch.empty(c, dtype=torch.float32, device=dev)
         training = bn.training or not bn.track_running_stats
         if training:
-            if bn.momentum is None:
-                raise NotImplementedError('BatchNorm2d(momentum=None) is not supported')
+            run = _RunningStats(bn, bn.training and bn.track_running_stats)
             stats = torch.zeros((2, c), dtype=torch.float32, device=dev)
             check(L.saicv_bn_stats(dtype_code(dt), ptr(x), M, c, ptr(stats[0]), ptr(stats[1]), st), 'bn_stats')
             mean = torch.empty(c, dtype=torch.float32, device=dev)
             invstd = torch.empty(c, dtype=torch.float32, device=dev)
-            track = bn.training and bn.track_running_stats and bn.running_mean is not None
-            nbt = bn.num_batches_tracked if (track and bn.num_batches_tracked is not None) else None
-            ws = torch.empty(L.saicv_bn_ws_floats(c), dtype=torch.float32, device=dev)
-            check(L.saicv_bn_finalize_fwd(ptr(stats[0]), ptr(stats[1]), 1, c, float(M), ptr(gamma), ptr(beta),
-                                          ptr(bn.running_mean) if track else 0, ptr(bn.running_var) if track else 0,
-                                          float(bn.momentum), float(bn.eps), ptr(mean), ptr(invstd), ptr(scale), ptr(shift), ptr(ws),
-                                          ptr(nbt), st), 'bn_finalize_fwd')
+            run.finalize(stats[0], stats[1], 1, c, M, gamma, beta, mean, invstd, scale, shift, st)
         else:
             check(L.saicv_bn_eval_coeffs(c, ptr(gamma), ptr(beta), ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps),
                                          ptr(scale), ptr(shift), st), 'bn_eval_coeffs')
@@ -1343,9 +1343,7 @@ class GroupNormFn(torch.autograd.Function):
         x, weight, bias, mean_rstd, ab = ctx.saved_tensors
         groups, relu = ctx.cfg
         n, c, h, w = x.shape
-        dy = _nhwc(dy)
-        if dy.dtype != x.dtype:
-            dy = dy.to(x.dtype)
+        dy = _nhwc(dy, x.dtype)
         dev = x.device
         dx = torch.empty_like(x)
         want_w = weight is not None and ctx.needs_input_grad[1]
