@@ -636,7 +636,7 @@ int window_unpartition(int dtype, const void* win, const void* addend, void* out
 static int relpos_fill(RelPosParams& p, const char* who, int dtype, const void* q, long q_rs, long q_bs, const float* tab_h,
                        const float* tab_w, int B, int heads, int Sh, int Sw) {
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
-    SAICV_REQUIRE(B > 0 && heads > 0 && Sh > 0 && Sw > 0 && Sh <= 128 && 2 * Sw - 1 <= 128, "%s: B=%d heads=%d Sh=%d Sw=%d (sizes up to 64 x 64)", who, B, heads, Sh, Sw);
+    SAICV_REQUIRE(B > 0 && heads > 0 && Sh > 0 && Sw > 0 && Sh <= 128 && 2 * Sw - 1 <= 128, "%s: B=%d heads=%d Sh=%d Sw=%d (admitted: Sh <= 128, Sw <= 64)", who, B, heads, Sh, Sw);
     SAICV_REQUIRE(q_rs % n == 0 && q_bs % n == 0, "%s: q strides must keep rows 16-byte aligned", who);
     p.q = q; p.q_rs = q_rs; p.q_bs = q_bs; p.tab_h = tab_h; p.tab_w = tab_w; p.B = B; p.heads = heads; p.Sh = Sh; p.Sw = Sw;
     return 0;

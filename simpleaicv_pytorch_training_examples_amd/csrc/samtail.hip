@@ -250,11 +250,11 @@ __global__ __launch_bounds__(ST_THREADS) void stats_up4_kernel(const T* __restri
 // 16 x 16 low-resolution pixels.  One thread per low pixel on its own would evaluate the loss gradient of every output pixel in
 // each of the (up to four) low pixels it feeds AND once more per row / column of the 8 x 8 window that only carries a zero
 // weight -- 64 evaluations per low pixel, 4 per output pixel, each ~60 vector operations with three transcendentals (that form
-// measured 1.7 ms per call at 20 x 4 x 256 x 256).  Here the 72 x 72 output pixels that touch the tile are evaluated ONCE into
-// LDS (1.27 per output pixel), from an 18 x 18 LDS copy of the low-resolution neighbourhood, and each thread then gathers its
+// measured 1.7 ms per call at 20 x 4 x 256 x 256).  Here the 68 x 68 output pixels that touch the tile are evaluated ONCE into
+// LDS (1.13 per output pixel), from an 18 x 18 LDS copy of the low-resolution neighbourhood, and each thread then gathers its
 // 8 x 8 window with the bilinear weights.
 constexpr int GU_T = 16;                  // low-resolution tile edge
-constexpr int GU_H = 4 * GU_T + 8;        // output pixels touching the tile, per axis (72)
+constexpr int GU_H = 4 * GU_T + 4;        // output pixels touching the tile, per axis: 4 i0 - 2 ... 4 (i0 + GU_T - 1) + 5 (68)
 template <typename T>
 __global__ __launch_bounds__(GU_T * GU_T) void grad_up4_tiled_kernel(const T* __restrict__ low, const float* __restrict__ targets,
                                                                      const float* __restrict__ coef, T* __restrict__ dlow, int M,
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(GU_T * GU_T) void grad_up4_tiled_kernel(const T* __
         lowt[a][c] = to_f32(lp[(size_t)r * w + cc]);
     }
     __syncthreads();
-    // output pixels (d, e) with d in [4 i0 - 2, 4 i0 + 4 GU_T + 5] (clipped to the image): their gradient, once
+    // output pixels (d, e) with d in [4 i0 - 2, 4 i0 + 4 GU_T + 1] (clipped to the image): their gradient, once
     const int D0 = 4 * i0 - 2, E0 = 4 * j0 - 2;
     for (int q = threadIdx.x; q < GU_H * GU_H; q += GU_T * GU_T) {
         const int dd = q / GU_H, ee = q - dd * GU_H;
