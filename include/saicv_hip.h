@@ -440,6 +440,29 @@ int saicv_mask_loss_stats_up4(int dtype, const void* low, const float* targets, 
 int saicv_mask_loss_grad_up4(int dtype, const void* low, const float* targets, const float* coef, void* dlow, int B, int M,
                              int h, int w, double alpha, double gamma, void* stream);
 
+/* ---- semantic segmentation (semantic_segmentation/losses.py:13-43 CELoss; models/pfan_semantic_segmentation.py:68-122 CPFE) ---- */
+/* Per-pixel clamped softmax cross-entropy over logits [rows][C] (bf16 or fp32, contiguous rows = the NHWC view of the prediction,
+ * 16-byte aligned, 1 <= C <= 256) and labels fp32 [rows] holding class ids:  p_t = exp(x_t - lse),
+ * loss = mean over rows of -log(clamp(p_t, 1e-4, 1 - 1e-4)).  A label outside [0, C) adds neither loss nor gradient and still
+ * counts in rows.  Writes lse [rows], `partial` (saicv_pixel_softmax_ce_ws_floats(rows) floats of workspace) and the scalar loss;
+ * the mean is an ordered two-stage sum (no atomics).  No gradient and no one-hot tensor is written. */
+size_t saicv_pixel_softmax_ce_ws_floats(size_t rows);
+int saicv_pixel_softmax_ce_fwd(int dtype, const void* logits, const float* label, size_t rows, int C, float* lse, float* partial,
+                               float* loss, void* stream);
+/* dlogits[r][c] = upstream[0] * (p_c - [c == t]) / rows where 1e-4 <= p_t <= 1 - 1e-4, else the whole row is 0 (the backward of
+ * torch.clamp); dlogits has the dtype and layout of logits; upstream is a device scalar */
+int saicv_pixel_softmax_ce_bwd(int dtype, const void* logits, const float* label, const float* lse, const float* upstream,
+                               size_t rows, int C, void* dlogits, void* stream);
+/* CPFE tap gather.  Z [N*H*W][ldz] fp32 is x . W_all^T, W_all rows = (1x1 weight [P] | per dilated branch j its nine taps, tap-major
+ * [9][P]); out [N][H][W][(1 + nb) P] (dtype) is the concatenated block output: out[.., 0:P] = Z[.., 0:P],
+ * out[n,h,w, P(1+j)+k] = sum_t Z[n, h+(ty-1)d_j, w+(tx-1)d_j, P + 9P j + P t + k] (fp32 sum, taps outside the image are zero).
+ * P % 4 == 0, 1 <= nb <= 3 branches with dilations d0, d1, d2.  The backward writes the dense dZ [N*H*W][(1 + 9 nb) P] (dtype)
+ * from dout [N][H][W][(1 + nb) P]: the transposed gather.  Neither direction uses atomics. */
+int saicv_cpfe_gather_fwd(int dtype, const float* z, long ldz, void* out, int N, int H, int W, int P, int nb, int d0, int d1,
+                          int d2, void* stream);
+int saicv_cpfe_gather_bwd(int dtype, const void* dout, void* dz, int N, int H, int W, int P, int nb, int d0, int d1, int d2,
+                          void* stream);
+
 /* Streaming attention (any Nq / Nk, head dim 32 or 64, separate q / k / v with strides).
  * Replaces SAM Attention.forward + add_decomposed_rel_pos (reference interactive_segmentation/models/
  * segment_anything/image_encoder.py:116-184) and DETR's nn.MultiheadAttention calls with a float

@@ -225,6 +225,11 @@ SIGNATURES = {
     'saicv_comm_join': (c_int, [_P, _P]),
     'saicv_comm_stats': (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(ctypes.c_ulonglong), POINTER(ctypes.c_ulonglong)]),
     'saicv_comm_destroy': (c_int, [_P]),
+    'saicv_pixel_softmax_ce_ws_floats': (c_size_t, [c_size_t]),
+    'saicv_pixel_softmax_ce_fwd': (c_int, [c_int, _P, _P, c_size_t, c_int, _P, _P, _P, _P]),
+    'saicv_pixel_softmax_ce_bwd': (c_int, [c_int, _P, _P, _P, _P, c_size_t, c_int, _P, _P]),
+    'saicv_cpfe_gather_fwd': (c_int, [c_int, _P, c_long, _P] + [c_int] * 8 + [_P]),
+    'saicv_cpfe_gather_bwd': (c_int, [c_int, _P, _P] + [c_int] * 8 + [_P]),
     'saicv_attention_stream_fwd': (c_int, [c_int, c_int, _PA, _P]),
     'saicv_attention_stream_bwd': (c_int, [c_int, c_int, _PA, _P]),
 }

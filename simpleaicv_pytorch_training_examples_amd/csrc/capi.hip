@@ -524,6 +524,25 @@ int saicv_mask_loss_grad_up4(int dtype, const void* low, const float* targets, c
                              int h, int w, double alpha, double gamma, void* stream) {
     return mask_loss_grad_up4(dtype, low, targets, coef, dlow, B, M, h, w, alpha, gamma, S(stream));
 }
+size_t saicv_pixel_softmax_ce_ws_floats(size_t rows) { return pixel_softmax_ce_ws_floats(rows); }
+int saicv_pixel_softmax_ce_fwd(int dtype, const void* logits, const float* label, size_t rows, int C, float* lse, float* partial,
+                               float* loss, void* stream) {
+    return pixel_softmax_ce_fwd(dtype, logits, label, rows, C, lse, partial, loss, S(stream));
+}
+int saicv_pixel_softmax_ce_bwd(int dtype, const void* logits, const float* label, const float* lse, const float* upstream,
+                               size_t rows, int C, void* dlogits, void* stream) {
+    return pixel_softmax_ce_bwd(dtype, logits, label, lse, upstream, rows, C, dlogits, S(stream));
+}
+int saicv_cpfe_gather_fwd(int dtype, const float* z, long ldz, void* out, int N, int H, int W, int P, int nb, int d0, int d1,
+                          int d2, void* stream) {
+    const int dil[3] = {d0, d1, d2};
+    return cpfe_gather_fwd(dtype, z, ldz, out, N, H, W, P, nb, dil, S(stream));
+}
+int saicv_cpfe_gather_bwd(int dtype, const void* dout, void* dz, int N, int H, int W, int P, int nb, int d0, int d1, int d2,
+                          void* stream) {
+    const int dil[3] = {d0, d1, d2};
+    return cpfe_gather_bwd(dtype, dout, dz, N, H, W, P, nb, dil, S(stream));
+}
 int saicv_attention_stream_fwd(int dtype, int D, const saicv_attn_desc* desc, void* stream) {
     if (!desc) { set_error("attention_stream: null descriptor"); return -1; }
     return attention_stream(dtype, D, 0, desc, S(stream));

@@ -77,6 +77,15 @@ int mask_loss_stats_up4(int dtype, const void* low, const float* targets, float*
                         double alpha, double gamma, double thr, hipStream_t st);
 int mask_loss_grad_up4(int dtype, const void* low, const float* targets, const float* coef, void* dlow, int B, int M, int h,
                        int w, double alpha, double gamma, hipStream_t st);
+// semseg.hip
+size_t pixel_softmax_ce_ws_floats(size_t rows);
+int pixel_softmax_ce_fwd(int dtype, const void* logits, const float* label, size_t rows, int C, float* lse, float* partial,
+                         float* loss, hipStream_t st);
+int pixel_softmax_ce_bwd(int dtype, const void* logits, const float* label, const float* lse, const float* upstream, size_t rows,
+                         int C, void* dlogits, hipStream_t st);
+int cpfe_gather_fwd(int dtype, const float* z, long ldz, void* out, int N, int H, int W, int P, int nb, const int* dil,
+                    hipStream_t st);
+int cpfe_gather_bwd(int dtype, const void* dout, void* dz, int N, int H, int W, int P, int nb, const int* dil, hipStream_t st);
 // attn_stream.hip: which = 0 forward, 1 dQ pass, 2 dK/dV pass; desc = const saicv_attn_desc*
 int attention_stream(int dtype, int D, int which, const void* desc, hipStream_t st);
 

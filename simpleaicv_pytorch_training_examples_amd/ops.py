@@ -277,6 +277,34 @@ def resize_bilinear_add(top, lateral):
     return ResizeBilinearAddFn.apply(top, lateral)
 
 
+class ResizeBilinearFn(torch.autograd.Function):
+    """F.interpolate(x, size=(H, W), mode='bilinear') on NHWC data: the merge kernel above without a lateral (reference
+    SimpleAICV/semantic_segmentation/models/pfan_semantic_segmentation.py:275-295); fp32 output, fixed-order gather backward."""
+
+    @staticmethod
+    def forward(ctx, x, H, W):
+        require_gpu(x)
+        x = _nhwc(x)
+        n, c, h, w = x.shape
+        out = _empty_nhwc(n, c, H, W, torch.float32, x.device)
+        check(lib().saicv_resize_bilinear_add_fwd(dtype_code(x.dtype), _lib.F32, ptr(x), 0, ptr(out), n, h, w, H, W, c, stream()),
+              'resize_bilinear_fwd')
+        ctx.geom = (n, c, h, w, H, W, x.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        n, c, h, w, H, W, dt = ctx.geom
+        dout = _nhwc(dout.float())
+        dx = _empty_nhwc(n, c, h, w, dt, dout.device)
+        check(lib().saicv_resize_bilinear_bwd(dtype_code(dt), ptr(dout), ptr(dx), n, h, w, H, W, c, stream()), 'resize_bilinear_bwd')
+        return dx, None, None
+
+
+def resize_bilinear(x, size):
+    return ResizeBilinearFn.apply(x, int(size[0]), int(size[1]))
+
+
 _desc_cache = {}
 
 
@@ -1007,7 +1035,10 @@ class ConvFn(torch.autograd.Function):
             if ctx.needs_input_grad[1]:
                 dwt = _conv_weight_grad(dp, dyp, x, weight, st)[:k].to(weight.dtype)
             if bias is not None and ctx.needs_input_grad[2]:
-                db = dy.float().sum((0, 2, 3)).to(bias.dtype)
+                # one column sum over the [pixels, k] view of the NHWC gradient, fp32 accumulation without an fp32 copy.  At a
+                # million pixels and 151 classes this ATen reduction is the largest kernel of the segmentation step (16.1 ms of
+                # 26.1 ms; saicv_colsum on dyp does it in a step of 10.1 ms): DESIGN.md section 3m has the numbers and why it stays
+                db = torch.sum(dy.permute(0, 2, 3, 1).reshape(-1, k), dim=0, dtype=torch.float32).to(bias.dtype)
             return dx, dwt, db, None, None
         M = n * d.OH * d.OW
         flops = 2.0 * M * k * d.R * d.S * c
@@ -1534,6 +1565,116 @@ class SoftmaxCEFn(torch.autograd.Function):
 
 def softmax_cross_entropy(logits, label, soft=False):
     return SoftmaxCEFn.apply(logits, label, soft)
+
+
+class PixelSoftmaxCEFn(torch.autograd.Function):
+    """The reference's semantic-segmentation CELoss (SimpleAICV/semantic_segmentation/losses.py:13-43) as one kernel each way
+    (csrc/semseg.hip): softmax over the class axis, clamp to [1e-4, 1 - 1e-4], -log at the labelled class, mean over the pixels.
+    The logits stay in their dtype (bf16 or fp32) and NHWC layout -- no fp32 copy, no permute, no one-hot; the forward keeps the
+    per-pixel log-sum-exp, the backward reads the logits once and writes the gradient once.  No host read: the step can be captured."""
+
+    @staticmethod
+    def forward(ctx, logits, label):
+        require_gpu(logits, label)
+        if logits.dim() == 4:
+            logits = _nhwc(logits)
+            n, c, h, w = logits.shape
+            rows = n * h * w
+        elif logits.dim() == 2:
+            logits = logits.contiguous()
+            rows, c = logits.shape
+        else:
+            raise ValueError('pixel_softmax_ce expects [B, C, H, W] logits or their [rows, C] NHWC view')
+        if logits.data_ptr() % 16:
+            logits = logits.clone(memory_format=torch.preserve_format)
+        label = label.reshape(-1).float().contiguous()
+        if label.numel() != rows:
+            raise ValueError(f'pixel_softmax_ce: {rows} pixels but {label.numel()} labels')
+        L, dev = lib(), logits.device
+        lse = torch.empty(rows, dtype=torch.float32, device=dev)
+        partial = torch.empty(L.saicv_pixel_softmax_ce_ws_floats(rows), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        nbytes = rows * c * logits.element_size()
+        t0 = KernelTimer.begin('pixel_ce')
+        check(L.saicv_pixel_softmax_ce_fwd(dtype_code(logits.dtype), ptr(logits), ptr(label), rows, c, ptr(lse), ptr(partial),
+                                           ptr(loss), stream()), 'pixel_softmax_ce_fwd')
+        KernelTimer.end(t0, 'pixel_ce', 0, nbytes)
+        ctx.save_for_backward(logits, label, lse)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, label, lse = ctx.saved_tensors
+        rows, c = lse.numel(), logits.shape[1]
+        gout = gout.float().contiguous()
+        dlog = torch.empty_like(logits)                      # preserves the NHWC strides of a 4-d prediction
+        t0 = KernelTimer.begin('pixel_ce')
+        check(lib().saicv_pixel_softmax_ce_bwd(dtype_code(logits.dtype), ptr(logits), ptr(label), ptr(lse), ptr(gout), rows, c,
+                                               ptr(dlog), stream()), 'pixel_softmax_ce_bwd')
+        KernelTimer.end(t0, 'pixel_ce', 0, 2 * rows * c * logits.element_size())
+        return dlog, None
+
+
+def pixel_softmax_ce(logits, label):
+    """logits: [B, C, H, W] (any strides; NHWC memory is used as it is) or the [rows, C] NHWC view, bf16 or fp32, C <= 256;
+    label: float (or integer) class ids, [B, H, W] or [rows].  -> scalar fp32 loss.
+    A label outside [0, C) contributes neither loss nor gradient and still counts in the mean's denominator (the rule of
+    softmax_cross_entropy); the reference's F.one_hot raises on such a label instead."""
+    return PixelSoftmaxCEFn.apply(logits, label)
+
+
+class CpfeConvsFn(torch.autograd.Function):
+    """x [N*H*W, Cin], W_all [(1 + 9 nb) P, Cin] -> the concatenated CPFE block output [N, (1 + nb) P, H, W] in `dtype`, NHWC
+    memory: LinearFn's GEMM with fp32 output (Z), then the tap gather of csrc/semseg.hip.  One node for both, so that the
+    backward's transposed gather hands dZ to the GEMM's gradient kernels in the compute dtype they read: between two nodes
+    autograd would cast it to Z's fp32 and LinearFn back again, two passes over M x 28 P more."""
+
+    @staticmethod
+    def forward(ctx, x, w_all, n, h, w, p, dilations, dtype):
+        nb = len(dilations)
+        z = LinearFn.forward(ctx, x, w_all, None, True)       # saves (x, w_all) and its descriptor on ctx
+        if z.shape != (n * h * w, (1 + 9 * nb) * p):
+            raise ValueError('cpfe convs: W_all must hold (1 + 9 * branches) * P rows and x N*H*W rows')
+        d = list(dilations) + [1] * (3 - nb)
+        out = _empty_nhwc(n, (1 + nb) * p, h, w, dtype, z.device)
+        t0 = KernelTimer.begin('cpfe_gather')
+        check(lib().saicv_cpfe_gather_fwd(dtype_code(dtype), ptr(z), z.stride(0), ptr(out), n, h, w, p, nb, d[0], d[1], d[2], stream()),
+              'cpfe_gather_fwd')
+        KernelTimer.end(t0, 'cpfe_gather', 0, z.numel() * 4 + out.numel() * out.element_size())
+        ctx.gather = (n, h, w, p, nb, d, dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        n, h, w, p, nb, d, dtype = ctx.gather
+        dout = _nhwc(dout, dtype)
+        dz = torch.empty((n * h * w, (1 + 9 * nb) * p), dtype=dtype, device=dout.device)
+        t0 = KernelTimer.begin('cpfe_gather')
+        check(lib().saicv_cpfe_gather_bwd(dtype_code(dtype), ptr(dout), ptr(dz), n, h, w, p, nb, d[0], d[1], d[2], stream()),
+              'cpfe_gather_bwd')
+        KernelTimer.end(t0, 'cpfe_gather', 0, (dz.numel() + dout.numel()) * dz.element_size())
+        dx, dw, _, _ = LinearFn.backward(ctx, dz)
+        return dx, dw, None, None, None, None, None, None
+
+
+def cpfe_convs(x, w_1x1, w_dilated, dilations):
+    """The four convolutions of a CPFE block (reference semantic_segmentation/models/pfan_semantic_segmentation.py:68-122) on one
+    input: conv 1x1 and, per entry of `w_dilated`, conv 3x3 with dilation = padding = dilations[j], all Cin -> P without bias,
+    concatenated along the channels -> [N, (1 + len(w_dilated)) * P, H, W] over NHWC memory, in the compute dtype.
+    Because P << Cin, all of them are ONE GEMM Z = x . W_all^T over the stacked weight rows (fp32 output) plus a gather that sums
+    each dilated branch's nine shifted taps.  W_all is assembled with torch ops, so every weight receives its own gradient."""
+    require_gpu(x, w_1x1)
+    if len(w_dilated) != len(dilations) or not 1 <= len(dilations) <= 3:
+        raise ValueError('cpfe_convs: one dilation per dilated weight, 1 to 3 of them')
+    dt = compute_dtype()
+    x = _nhwc(x, dt)
+    n, cin, h, w = x.shape
+    p = w_1x1.shape[0]
+    for wt in w_dilated:
+        if tuple(wt.shape) != (p, cin, 3, 3):
+            raise ValueError(f'cpfe_convs: a dilated weight is {tuple(wt.shape)}, expected {(p, cin, 3, 3)}')
+    w_all = torch.cat([w_1x1.reshape(p, cin).float()] + [wt.float().permute(2, 3, 0, 1).reshape(9 * p, cin) for wt in w_dilated], dim=0)
+    return CpfeConvsFn.apply(x.permute(0, 2, 3, 1).reshape(n * h * w, cin), w_all, n, h, w, p, tuple(int(d) for d in dilations), dt)
 
 
 # ------------------------------------------------------------------------------ Muon: grouped Newton-Schulz (csrc/muon.hip)

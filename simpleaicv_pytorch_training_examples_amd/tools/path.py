@@ -16,3 +16,5 @@ Objects365_path = os.path.join(_ROOT, 'objects365_2020')
 VOCdataset_path = os.path.join(_ROOT, 'VOCdataset')
 # interactive segmentation
 interactive_segmentation_dataset_path = os.path.join(_ROOT, 'interactive_segmentation_dataset')
+# semantic segmentation
+ADE20Kdataset_path = os.path.join(_ROOT, 'ADE20K')

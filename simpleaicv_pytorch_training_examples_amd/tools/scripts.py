@@ -7,6 +7,7 @@
                                                variant needs pycocotools, which the bench image does not have)
   train_detection                              (reference :900-1092)
   train_mae_self_supervised_learning           (reference :1774-1934)
+  semantic_segmentation_areas / test_semantic_segmentation / train_semantic_segmentation   (reference :1095-1451)
 
 Loop semantics are kept -- skip a batch when ANY rank saw inf/nan input or a zero/inf/nan loss,
 gradient accumulation with `no_sync()`, optional clipping, GradScaler step/update, EMA, mean-
@@ -519,6 +520,103 @@ def train_mae_self_supervised_learning(train_loader, model, criterion, optimizer
         return (data['image'].to(device, non_blocking=True), data['label'].to(device, non_blocking=True))
     return _epoch_loop(train_loader, model, optimizer, scheduler, epoch, logger, config, step_fn, 'loss', 5, graph_inputs,
                        log_terms=False)
+
+
+# ---------------------------------------------------------------------------------------------- semantic segmentation
+def semantic_segmentation_areas(pred_ids, mask, sizes, num_classes):
+    """Per-class pixel counts of one batch, float64 [4, num_classes]: intersection, prediction, ground truth, union -- what the
+    reference takes per image with torch.histc(bins=num_classes, min=0, max=num_classes - 1) over the top-left
+    int(size[0]) x int(size[1]) crop (reference tools/scripts.py:1138-1171), summed over the batch.  pred_ids [B, H, W] integer class
+    ids, mask [B, H, W] class ids (float, as the collater delivers them), sizes [B, 2] (h, w).  Ids outside [0, num_classes) are
+    not counted (histc ignores values outside its range).  Pure tensor code: runs on the tensors' device, CPU included."""
+    dev = pred_ids.device
+    b, h, w = pred_ids.shape
+    hw = torch.as_tensor(np.asarray(sizes), dtype=torch.float32).to(dev).long()              # int(size): truncation
+    inside = ((torch.arange(h, device=dev).view(1, h, 1) < hw[:, 0].view(b, 1, 1))
+              & (torch.arange(w, device=dev).view(1, 1, w) < hw[:, 1].view(b, 1, 1)))
+    pred, gt = pred_ids.long(), mask.long()
+
+    def count(ids, select):
+        select = select & (ids >= 0) & (ids < num_classes)
+        return torch.bincount(ids[select], minlength=num_classes).double()
+
+    area_pred, area_gt = count(pred, inside), count(gt, inside)
+    intersect = count(pred, inside & (pred == mask))
+    return torch.stack([intersect, area_pred, area_gt, area_pred + area_gt - intersect])
+
+
+def test_semantic_segmentation(test_loader, model, criterion, config):
+    """reference :1095-1259: loss, argmax over the classes, per-class areas accumulated on the device in float64, then mean
+    precision / recall / IoU / Dice over the classes that occur in the ground truth (x 100)."""
+    batch_time, data_time, losses = AverageMeter(), AverageMeter(), AverageMeter()
+    if getattr(config, 'use_ema_model', False):
+        model = config.ema_model.ema_model
+    model.eval()
+    device = _device_of(model)
+    sync = torch.cuda.synchronize if device.type == 'cuda' else (lambda: None)
+    areas = torch.zeros((4, config.num_classes), dtype=torch.float64, device=device)
+    with torch.no_grad():
+        end = time.time()
+        for data in test_loader:
+            images, masks, sizes = data['image'].to(device), data['mask'].to(device), data['size']
+            sync()
+            data_time.update(time.time() - end)
+            end = time.time()
+            outputs = model(images)
+            sync()
+            batch_time.update(time.time() - end)
+            losses.update(float(criterion(outputs, masks)), images.size(0))
+            areas += semantic_segmentation_areas(torch.argmax(outputs, dim=1), masks, sizes, config.num_classes)
+            end = time.time()
+    per_gpu = config.batch_size // config.gpus_num
+    result_dict = collections.OrderedDict()
+    result_dict['test_loss'] = losses.avg
+    result_dict['per_image_load_time'] = f'{data_time.avg / per_gpu * 1000:.3f}ms'
+    result_dict['per_image_inference_time'] = f'{batch_time.avg / per_gpu * 1000:.3f}ms'
+    intersect, area_pred, area_gt, union = areas.cpu().tolist()
+    exist_num_class, sums = 0., [0., 0., 0., 0.]
+    for i, p, g, u in zip(intersect, area_pred, area_gt, union):
+        if g == 0:
+            continue
+        exist_num_class += 1.
+        for j, (num, den) in enumerate(((i, p), (i, g), (i, u), (2. * i, p + g))):
+            if den != 0:
+                sums[j] += num / den * 100.
+    if exist_num_class > 0:
+        sums = [v / exist_num_class for v in sums]
+    result_dict['exist_num_class'] = exist_num_class
+    for name, v in zip(('mean_precision', 'mean_recall', 'mean_iou', 'mean_dice'), sums):
+        result_dict[name] = v
+    return result_dict
+
+
+def train_semantic_segmentation(train_loader, model, criterion, optimizer, scheduler, epoch, logger, config):
+    '''train semantic segmentation model for one epoch (reference tools/scripts.py:1262-1451): `outputs = model(images)`, one loss
+    per entry of the criterion dict scaled by config.loss_ratio, the reference's skip / accumulation / clipping / scaler / EMA /
+    scheduler semantics and its log line `train: epoch 0001, iter [00100, 00631], lr: 0.000100, loss: 2.1042, CELoss: 2.1042, `.
+    The iteration has static shapes and no host read (the fused loss decides the clamp on the device): with config.use_step_graph
+    it is captured whole and replayed.'''
+    model.train()
+    device = _device_of(model)
+    amp_type = get_amp_type(model)
+    if config.local_rank == 0 and getattr(config, 'total_rank', 0) == 0:
+        logger.info(f'use_amp: {config.use_amp}, amp_type: {amp_type}!')
+
+    def step_fn(data):
+        if isinstance(data, tuple):                      # captured step: static device buffers
+            images, masks = data
+        else:
+            images = data['image'].to(device, non_blocking=True)
+            masks = data['mask'].to(device, non_blocking=True)
+        bad = any_nonfinite(images, masks)
+        with autocast(device_type=device.type, dtype=amp_type, enabled=bool(config.use_amp)):
+            outputs = model(images)
+            loss_value = {name: config.loss_ratio[name] * criterion[name](outputs, masks) for name in criterion.keys()}
+        return bad, loss_value, images.size(0)
+
+    def graph_inputs(data):
+        return (data['image'].to(device, non_blocking=True), data['mask'].to(device, non_blocking=True))
+    return _epoch_loop(train_loader, model, optimizer, scheduler, epoch, logger, config, step_fn, 'loss', 5, graph_inputs)
 
 
 # ---------------------------------------------------------------------------------------------- detection evaluation
