@@ -463,6 +463,32 @@ int saicv_cpfe_gather_fwd(int dtype, const float* z, long ldz, void* out, int N,
 int saicv_cpfe_gather_bwd(int dtype, const void* dout, void* dz, int N, int H, int W, int P, int nb, int d0, int d1, int d2,
                           void* stream);
 
+/* ---- salient object detection (salient_object_detection/models/pfan_segmentation.py:254-300 pred_conv + float() + sigmoid;
+ *      salient_object_detection/losses.py:16-134 BCELoss / BCEIouloss / BCEDiceLoss) ---- */
+/* One-channel 3x3 convolution head, stride 1, pad 1.  x NHWC [N][H][W][C] (dtype: bf16 or fp32; C % 8 == 0, 8 <= C <= 64; 16-byte
+ * aligned), weight the fp32 parameter [1][C][3][3] read in place: element (c, tap = 3 r + s) lies at weight[c * wsc + tap * wsk]
+ * (contiguous: 9, 1; channels-last: 1, C), fp32 bias[1].  out fp32 [N][H][W] = conv + bias, through a sigmoid when `sigmoid` is
+ * set; accumulation in fp32, the logit is never rounded to the activation dtype. */
+int saicv_conv3x3_c1_fwd(int dtype, const void* x, const float* weight, long wsc, long wsk, const float* bias, float* out, int N,
+                         int H, int W, int C, int sigmoid, void* stream);
+/* Backward from dout fp32 [N][H][W]: dz = dout * p * (1 - p) with `sigmoid` set (p = the saved output), else dout.
+ * dx (dtype, layout of x; may be null) = sum over the taps of dz * w; dw (fp32, the weight's strides; may be null) and db (fp32
+ * [1]; may be null) are ordered two-stage sums: one partial row per workgroup in ws (saicv_conv3x3_c1_ws_floats floats), then one
+ * fixed-order fold that stores the result, or adds it to what dw / db hold when `accumulate` is set.  No atomics. */
+size_t saicv_conv3x3_c1_ws_floats(int N, int H, int W, int C);
+int saicv_conv3x3_c1_bwd(int dtype, const void* x, const float* weight, long wsc, long wsk, const float* p, const float* dout,
+                         void* dx, float* dw, float* db, float* ws, int N, int H, int W, int C, int sigmoid, int accumulate,
+                         void* stream);
+/* Binary mask statistics.  prob, label fp32 [B][P] (label anywhere in [0, 1]) -> stats [B][4] =
+ * (sum bce, sum ph, sum l, sum ph * l), ph = clamp(p, float32(1e-4), float32(1 - 1e-4)), bce = -(l log ph + (1 - l) log(1 - ph)).
+ * Ordered two-stage sums through `partial` (saicv_binary_seg_stats_ws_floats floats); no atomics. */
+size_t saicv_binary_seg_stats_ws_floats(int B, size_t P);
+int saicv_binary_seg_stats_fwd(const float* prob, const float* label, int B, size_t P, float* partial, float* stats, void* stream);
+/* dprob[b][i] = g[b][0] * (-l / p + (1 - l) / (1 - p)) + g[b][1] + g[b][3] * l where lo <= p <= hi, exactly 0 elsewhere (the
+ * backward of torch.clamp on the fp32 input); g = dL/dstats, a device tensor [B][4] */
+int saicv_binary_seg_stats_bwd(const float* prob, const float* label, const float* gstats, int B, size_t P, float* dprob,
+                               void* stream);
+
 /* Streaming attention (any Nq / Nk, head dim 32 or 64, separate q / k / v with strides).
  * Replaces SAM Attention.forward + add_decomposed_rel_pos (reference interactive_segmentation/models/
  * segment_anything/image_encoder.py:116-184) and DETR's nn.MultiheadAttention calls with a float

@@ -230,6 +230,12 @@ SIGNATURES = {
     'saicv_pixel_softmax_ce_bwd': (c_int, [c_int, _P, _P, _P, _P, c_size_t, c_int, _P, _P]),
     'saicv_cpfe_gather_fwd': (c_int, [c_int, _P, c_long, _P] + [c_int] * 8 + [_P]),
     'saicv_cpfe_gather_bwd': (c_int, [c_int, _P, _P] + [c_int] * 8 + [_P]),
+    'saicv_conv3x3_c1_ws_floats': (c_size_t, [c_int] * 4),
+    'saicv_conv3x3_c1_fwd': (c_int, [c_int, _P, _P, c_long, c_long, _P, _P] + [c_int] * 5 + [_P]),
+    'saicv_conv3x3_c1_bwd': (c_int, [c_int, _P, _P, c_long, c_long] + [_P] * 6 + [c_int] * 6 + [_P]),
+    'saicv_binary_seg_stats_ws_floats': (c_size_t, [c_int, c_size_t]),
+    'saicv_binary_seg_stats_fwd': (c_int, [_P, _P, c_int, c_size_t, _P, _P, _P]),
+    'saicv_binary_seg_stats_bwd': (c_int, [_P, _P, _P, c_int, c_size_t, _P, _P]),
     'saicv_attention_stream_fwd': (c_int, [c_int, c_int, _PA, _P]),
     'saicv_attention_stream_bwd': (c_int, [c_int, c_int, _PA, _P]),
 }

@@ -543,6 +543,24 @@ int saicv_cpfe_gather_bwd(int dtype, const void* dout, void* dz, int N, int H, i
     const int dil[3] = {d0, d1, d2};
     return cpfe_gather_bwd(dtype, dout, dz, N, H, W, P, nb, dil, S(stream));
 }
+size_t saicv_conv3x3_c1_ws_floats(int N, int H, int W, int C) { return conv3x3_c1_ws_floats(N, H, W, C); }
+int saicv_conv3x3_c1_fwd(int dtype, const void* x, const float* weight, long wsc, long wsk, const float* bias, float* out, int N,
+                         int H, int W, int C, int sigmoid, void* stream) {
+    return conv3x3_c1_fwd(dtype, x, weight, wsc, wsk, bias, out, N, H, W, C, sigmoid, S(stream));
+}
+int saicv_conv3x3_c1_bwd(int dtype, const void* x, const float* weight, long wsc, long wsk, const float* p, const float* dout,
+                         void* dx, float* dw, float* db, float* ws, int N, int H, int W, int C, int sigmoid, int accumulate,
+                         void* stream) {
+    return conv3x3_c1_bwd(dtype, x, weight, wsc, wsk, p, dout, dx, dw, db, ws, N, H, W, C, sigmoid, accumulate, S(stream));
+}
+size_t saicv_binary_seg_stats_ws_floats(int B, size_t P) { return binary_seg_stats_ws_floats(B, P); }
+int saicv_binary_seg_stats_fwd(const float* prob, const float* label, int B, size_t P, float* partial, float* stats, void* stream) {
+    return binary_seg_stats_fwd(prob, label, B, P, partial, stats, S(stream));
+}
+int saicv_binary_seg_stats_bwd(const float* prob, const float* label, const float* gstats, int B, size_t P, float* dprob,
+                               void* stream) {
+    return binary_seg_stats_bwd(prob, label, gstats, B, P, dprob, S(stream));
+}
 int saicv_attention_stream_fwd(int dtype, int D, const saicv_attn_desc* desc, void* stream) {
     if (!desc) { set_error("attention_stream: null descriptor"); return -1; }
     return attention_stream(dtype, D, 0, desc, S(stream));

@@ -86,6 +86,15 @@ int pixel_softmax_ce_bwd(int dtype, const void* logits, const float* label, cons
 int cpfe_gather_fwd(int dtype, const float* z, long ldz, void* out, int N, int H, int W, int P, int nb, const int* dil,
                     hipStream_t st);
 int cpfe_gather_bwd(int dtype, const void* dout, void* dz, int N, int H, int W, int P, int nb, const int* dil, hipStream_t st);
+// salient.hip
+size_t conv3x3_c1_ws_floats(int N, int H, int W, int C);
+int conv3x3_c1_fwd(int dtype, const void* x, const float* weight, long wsc, long wsk, const float* bias, float* out, int N, int H,
+                   int W, int C, int sigmoid, hipStream_t st);
+int conv3x3_c1_bwd(int dtype, const void* x, const float* weight, long wsc, long wsk, const float* p, const float* dout, void* dx,
+                   float* dw, float* db, float* ws, int N, int H, int W, int C, int sigmoid, int accumulate, hipStream_t st);
+size_t binary_seg_stats_ws_floats(int B, size_t P);
+int binary_seg_stats_fwd(const float* prob, const float* label, int B, size_t P, float* partial, float* stats, hipStream_t st);
+int binary_seg_stats_bwd(const float* prob, const float* label, const float* gstats, int B, size_t P, float* dprob, hipStream_t st);
 // attn_stream.hip: which = 0 forward, 1 dQ pass, 2 dK/dV pass; desc = const saicv_attn_desc*
 int attention_stream(int dtype, int D, int which, const void* desc, hipStream_t st);
 

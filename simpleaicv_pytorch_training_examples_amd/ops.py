@@ -7,6 +7,7 @@ and every parameter gradient are fp32, as under the reference's autocast region
 """
 import collections
 import ctypes
+import weakref
 
 import torch
 
@@ -1675,6 +1676,150 @@ def cpfe_convs(x, w_1x1, w_dilated, dilations):
             raise ValueError(f'cpfe_convs: a dilated weight is {tuple(wt.shape)}, expected {(p, cin, 3, 3)}')
     w_all = torch.cat([w_1x1.reshape(p, cin).float()] + [wt.float().permute(2, 3, 0, 1).reshape(9 * p, cin) for wt in w_dilated], dim=0)
     return CpfeConvsFn.apply(x.permute(0, 2, 3, 1).reshape(n * h * w, cin), w_all, n, h, w, p, tuple(int(d) for d in dilations), dt)
+
+
+# ------------------------------------------------------------------------------ salient object detection (csrc/salient.hip)
+C1_MIN_C, C1_MAX_C = 8, 64
+
+
+def conv3x3_c1_supports(cin):
+    """whether the one-channel head kernel takes `cin` input channels (a multiple of 8 from 8 to 64)"""
+    return C1_MIN_C <= cin <= C1_MAX_C and cin % 8 == 0
+
+
+class Conv3x3C1Fn(torch.autograd.Function):
+    """nn.Conv2d(C, 1, kernel_size=3, padding=1, bias=True) + .float() + sigmoid, the prediction head of the salient-object PFAN
+    (reference SimpleAICV/salient_object_detection/models/pfan_segmentation.py:254-300), as one streaming kernel each way
+    (csrc/salient.hip): x stays NHWC in its dtype, the fp32 weight is read in place (no packing launch), the output is fp32
+    [N, 1, H, W] and the logit is never rounded.  dw and db are ordered two-stage sums -- bit-reproducible in every mode -- and land
+    in the arena when the engine offers the slots."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, sigmoid):
+        require_gpu(x, weight, bias)
+        x = _nhwc(x)
+        if x.data_ptr() % 16:
+            x = x.clone(memory_format=torch.preserve_format)
+        n, c, h, w = x.shape
+        if tuple(weight.shape) != (1, c, 3, 3) or bias is None or bias.numel() != 1:
+            raise ValueError(f'conv3x3_c1: weight {tuple(weight.shape)} / bias do not describe a 3x3 convolution {c} -> 1 with bias')
+        if weight.dtype != torch.float32 or bias.dtype != torch.float32:
+            raise ValueError('conv3x3_c1: weight and bias are the fp32 parameters')
+        if not conv3x3_c1_supports(c):
+            raise ValueError(f'conv3x3_c1: {c} input channels; the kernel takes a multiple of 8 from {C1_MIN_C} to {C1_MAX_C}')
+        wuse = weight if weight.stride(2) == 3 * weight.stride(3) else weight.contiguous()
+        out = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device)
+        t0 = KernelTimer.begin('conv3x3_c1')
+        check(lib().saicv_conv3x3_c1_fwd(dtype_code(x.dtype), ptr(x), ptr(wuse), wuse.stride(1), wuse.stride(3), ptr(bias), ptr(out),
+                                         n, h, w, c, int(bool(sigmoid)), stream()), 'conv3x3_c1_fwd')
+        KernelTimer.end(t0, 'conv3x3_c1', 2.0 * n * h * w * 9 * c, x.numel() * x.element_size() + out.numel() * 4)
+        ctx.save_for_backward(x, weight, bias, out if sigmoid else None)
+        ctx.sigmoid = bool(sigmoid)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight, bias, out = ctx.saved_tensors
+        n, c, h, w = x.shape
+        dout = dout.float().contiguous()
+        L, dev = lib(), x.device
+        wuse = weight if weight.stride(2) == 3 * weight.stride(3) else weight.contiguous()
+        want_x, want_w, want_b = ctx.needs_input_grad[:3]
+        dx = torch.empty_like(x) if want_x else None
+        gw = _arena_grad(weight) if want_w and wuse is weight else None
+        gb = _arena_grad(bias) if want_b else None
+        # both sums leave one fold launch: they go straight into the arena only when every gradient that is wanted has a slot there
+        direct = (want_w or want_b) and (not want_w or gw is not None) and (not want_b or gb is not None)
+        if direct:
+            dw, db = gw, gb
+        else:
+            dw = torch.empty_strided(wuse.shape, wuse.stride(), dtype=torch.float32, device=dev) if want_w else None
+            db = torch.empty(bias.shape, dtype=torch.float32, device=dev) if want_b else None
+        ws = torch.empty(L.saicv_conv3x3_c1_ws_floats(n, h, w, c), dtype=torch.float32, device=dev)
+        t0 = KernelTimer.begin('conv3x3_c1')
+        check(L.saicv_conv3x3_c1_bwd(dtype_code(x.dtype), ptr(x), ptr(wuse), wuse.stride(1), wuse.stride(3), ptr(out), ptr(dout),
+                                     ptr(dx), ptr(dw), ptr(db), ptr(ws), n, h, w, c, int(ctx.sigmoid), int(direct), stream()),
+              'conv3x3_c1_bwd')
+        KernelTimer.end(t0, 'conv3x3_c1', 4.0 * n * h * w * 9 * c, (2 if want_x else 1) * x.numel() * x.element_size() + dout.numel() * 8)
+        if direct:
+            return dx, None, None, None
+        return dx, dw, db, None
+
+
+def conv3x3_c1(x, weight, bias, sigmoid=True):
+    """x [N, C, H, W] (NHWC memory is used as it is; bf16 or fp32, C a multiple of 8 from 8 to 64), weight the fp32 parameter
+    [1, C, 3, 3], bias fp32 [1] -> fp32 [N, 1, H, W]: sigmoid(conv(x) + b) or, with sigmoid=False, the logit.  Under autocast an
+    fp32 activation is cast to the autocast dtype first, as torch.autocast casts a convolution's operands."""
+    if torch.is_autocast_enabled('cuda') and x.is_floating_point() and x.dtype != compute_dtype():
+        x = x.to(compute_dtype())
+    return Conv3x3C1Fn.apply(x, weight, bias, sigmoid)
+
+
+class BinarySegStatsFn(torch.autograd.Function):
+    """prob, label fp32 [B, P] -> [B, 4] = (sum bce, sum ph, sum l, sum ph * l), ph = clamp(prob, 1e-4, 1 - 1e-4): everything the
+    reference's BCELoss / BCEIouloss / BCEDiceLoss (SimpleAICV/salient_object_detection/losses.py:16-134) read of the full-resolution
+    maps.  One read of both maps each way; the backward takes dL/dstats as a device tensor (no host read) and gives exactly 0
+    outside the clamp, as torch.clamp's backward does."""
+
+    @staticmethod
+    def forward(ctx, prob, label):
+        b, p = prob.shape
+        L, dev = lib(), prob.device
+        stats = torch.empty((b, 4), dtype=torch.float32, device=dev)
+        partial = torch.empty(L.saicv_binary_seg_stats_ws_floats(b, p), dtype=torch.float32, device=dev)
+        t0 = KernelTimer.begin('binary_seg_stats')
+        check(L.saicv_binary_seg_stats_fwd(ptr(prob), ptr(label), b, p, ptr(partial), ptr(stats), stream()), 'binary_seg_stats_fwd')
+        KernelTimer.end(t0, 'binary_seg_stats', 0, 8 * b * p)
+        ctx.save_for_backward(prob, label)
+        return stats
+
+    @staticmethod
+    def backward(ctx, g):
+        prob, label = ctx.saved_tensors
+        b, p = prob.shape
+        g = g.float().contiguous()
+        dprob = torch.empty_like(prob)
+        t0 = KernelTimer.begin('binary_seg_stats')
+        check(lib().saicv_binary_seg_stats_bwd(ptr(prob), ptr(label), ptr(g), b, p, ptr(dprob), stream()), 'binary_seg_stats_bwd')
+        KernelTimer.end(t0, 'binary_seg_stats', 0, 12 * b * p)
+        return dprob, None
+
+
+_bss_last = [None]        # (ref(prob), prob._version, ref(label), label._version, grad mode, stats): the last call only
+
+
+def _bss_forget(dead):
+    last = _bss_last[0]
+    if last is not None and (last[0] is dead or last[2] is dead):
+        _bss_last[0] = None
+
+
+def binary_seg_stats(prob, label):
+    """prob: fp32 contiguous probabilities [B, ...]; label: the soft mask with the same number of elements per sample, values in
+    [0, 1] -> stats [B, 4] = per sample (sum bce, sum ph, sum l, sum ph * l) over ph = clamp(prob, 1e-4, 1 - 1e-4).
+    A second call with the same `prob` object at the same `_version` and the same `label` returns the SAME stats tensor: a
+    criterion dict of several losses over one prediction costs one forward launch, and autograd adds the [B, 4] gradients before
+    the one backward launch.  Only the last call is remembered, and weakly: the entry refers to `prob` and `label` through weak
+    references and goes when either of them does, so it never outlives the prediction it describes (the [B, 4] result itself is
+    referenced: the losses keep only reductions of it alive, not the tensor)."""
+    require_gpu(prob, label)
+    if prob.dtype != torch.float32 or not prob.is_contiguous():
+        raise ValueError('binary_seg_stats: prob must be fp32 and contiguous')
+    last = _bss_last[0]
+    mode = (torch.is_grad_enabled(), prob.requires_grad)
+    if (last is not None and last[0]() is prob and last[1] == prob._version and last[2]() is label
+            and last[3] == label._version and last[4] == mode):
+        return last[5]
+    b = prob.shape[0]
+    p2 = prob.view(b, -1)
+    l2 = label.reshape(b, -1)
+    if l2.dtype != torch.float32 or not l2.is_contiguous():
+        l2 = l2.float().contiguous()
+    if l2.shape != p2.shape:
+        raise ValueError(f'binary_seg_stats: prob has {p2.shape[1]} elements per sample, label {l2.shape[1]}')
+    stats = BinarySegStatsFn.apply(p2, l2)
+    _bss_last[0] = (weakref.ref(prob, _bss_forget), prob._version, weakref.ref(label, _bss_forget), label._version, mode, stats)
+    return stats
 
 
 # ------------------------------------------------------------------------------ Muon: grouped Newton-Schulz (csrc/muon.hip)

@@ -18,3 +18,5 @@ VOCdataset_path = os.path.join(_ROOT, 'VOCdataset')
 interactive_segmentation_dataset_path = os.path.join(_ROOT, 'interactive_segmentation_dataset')
 # semantic segmentation
 ADE20Kdataset_path = os.path.join(_ROOT, 'ADE20K')
+# salient object detection
+salient_object_detection_dataset_path = os.path.join(_ROOT, 'salient_object_detection_dataset')

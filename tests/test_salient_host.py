@@ -1,0 +1,183 @@
+"""Host-side checks of the salient-object-detection family (no GPU): the float64 judges of tests/salient_common.py -- the loss judge
+against the values the REFERENCE losses produced, the head judge against F.conv2d + sigmoid under autograd -- EvalMeter against the
+reference's, the model factories and state_dict surface, the collater, the synthetic dataset and the benchmark config
+(tests/golden/pfan_sal_r18_tiny.pt is written by scripts/record_pfan_salient_golden.py)."""
+import importlib.util
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import salient_common as S
+from conftest import GOLDEN, ROOT
+
+
+@pytest.fixture(scope='module')
+def fx():
+    return torch.load(os.path.join(GOLDEN, 'pfan_sal_r18_tiny.pt'), weights_only=True)
+
+
+@pytest.mark.parametrize('case', S.LOSS_CASES)
+def test_loss_judge_reproduces_the_reference_losses(fx, case):
+    """pins the judge to the reference, not to the code under test; bound: the project's loss bound (tests/test_gpu_kernels.py)"""
+    B, P = case
+    p, label = S.loss_inputs(B, P)
+    stats = S.stats_judge(p, label)['stats']
+    for name in S.LOSS_NAMES:
+        ref = fx['loss_cases'][case][name]
+        got = float(S.loss_from_stats(stats, P, name))
+        print(case, name, got, ref)
+        assert abs(got - ref) <= 1e-5 * max(1., abs(ref)), (case, name, got, ref)
+
+
+def test_stats_judge_gradient_equals_autograd_of_the_reference_formulas():
+    p, label = S.loss_inputs(2, 4099)
+    p[0, :6] = torch.tensor([S.LO, S.HI, 0., 1., np.nextafter(np.float32(S.LO), np.float32(0)), np.nextafter(np.float32(S.HI), np.float32(1))])
+    g = torch.tensor([[0.7, -0.3, 9., 1.1], [-0.2, 0.5, 9., -0.4]], dtype=torch.float64)
+    j = S.stats_judge(p, label, g)
+    pa = p.double().requires_grad_(True)
+    ph = torch.clamp(pa, min=S.LO, max=S.HI)
+    l = label.double()
+    stats = torch.stack([(-(l * torch.log(ph) + (1. - l) * torch.log(1. - ph))).sum(1), ph.sum(1), l.sum(1), (ph * l).sum(1)], dim=1)
+    (stats * g).sum().backward()
+    assert float((stats.detach() - j['stats']).abs().max()) <= 1e-12 * float(j['stats'].abs().max())
+    assert float((pa.grad - j['dp']).abs().max()) <= 1e-12 * float(j['dp'].abs().max())
+    assert j['inside'][0, :2].all() and not j['inside'][0, 2:6].any()                  # the bounds themselves are inside
+    assert float(j['dp'][~j['inside']].abs().max()) == 0.0 and float(pa.grad[~j['inside']].abs().max()) == 0.0
+    assert bool((j['dp_mag'] >= j['dp'].abs() * (1 - 1e-12)).all())
+
+
+@pytest.mark.parametrize('sigmoid', [True, False])
+@pytest.mark.parametrize('shape', [(2, 8, 1, 1), (2, 16, 3, 5), (1, 32, 9, 11)])
+def test_head_judge_equals_conv2d_and_sigmoid_in_float64(shape, sigmoid):
+    N, C, H, W = shape
+    x, w, b, dout = S.head_operands(N, C, H, W, seed=H, integer=False)
+    j = S.head_judge(x, w, b, dout, sigmoid)
+    xa, wa, ba = x.double().requires_grad_(True), w.double().requires_grad_(True), b.double().requires_grad_(True)
+    out = F.conv2d(xa, wa, ba, stride=1, padding=1)
+    out = torch.sigmoid(out) if sigmoid else out
+    gx, gw, gb = torch.autograd.grad(out, [xa, wa, ba], dout.double())
+    for got, ref in ((j['out'], out.detach()), (j['dx'], gx), (j['dw'], gw), (j['db'], gb)):
+        assert got.shape == ref.shape and float((got - ref).abs().max()) <= 1e-12 * max(float(ref.abs().max()), 1e-30)
+
+
+def test_integer_head_operands_give_integer_sums_within_the_stated_bounds():
+    x, w, b, dout = S.head_operands(2, 64, 64, 96, seed=5, integer=True, dtype=torch.bfloat16)
+    assert set(x.float().unique().tolist()) <= {-1., 0., 1.} and float(b) in (-1., 0., 1.)
+    j = S.head_judge(x, w, b, dout, False)
+    for k in ('out', 'dx', 'dw', 'db'):
+        assert torch.equal(j[k], j[k].round())
+    assert float(j['out'].abs().max()) <= 577 and float(j['dw'].abs().max()) <= 12288 and float(j['db'].abs().max()) <= 12288
+
+
+def test_eval_meter_equals_the_reference_on_cpu_tensors(fx):
+    from simpleaicv_pytorch_training_examples_amd.tools.salient_object_detection_scripts import EvalMeter
+
+    class cfg:
+        thresh, squared_beta = S.EVAL_THRESH, S.EVAL_SQUARED_BETA
+    meter = EvalMeter(cfg)
+    for preds, masks in S.eval_inputs():
+        meter.add_batch_result(preds, masks)
+    meter.compute_all_metrics()
+    assert set(fx['eval']) == set(S.EVAL_KEYS)
+    for k in S.EVAL_KEYS:
+        got = np.asarray(getattr(meter, k))
+        assert got.dtype == (np.float32 if k != 'sample_num' else got.dtype), k
+        assert np.array_equal(got, np.asarray(fx['eval'][k], dtype=got.dtype)), (k, got, fx['eval'][k])
+
+
+def test_first_dataset_metric_follows_save_model_metric():
+    from simpleaicv_pytorch_training_examples_amd.tools.salient_object_detection_scripts import first_dataset_metric
+    result = {'A[+]B': {'miou_average': np.float32(0.25), 'miou_max': 0.5}, 'C': {'miou_average': 0.9}}
+    total, metric, test_loss = first_dataset_metric(result, 'miou_average', 0, 0.125)
+    assert total is result['A[+]B'] and metric == np.float32(0.25) and test_loss == 0.125
+    assert first_dataset_metric({}, 'miou_average', 3, 4) == (None, 3, 4)
+
+
+def test_factories_state_dict_surface_and_initial_weights_equal_the_reference(fx):
+    from simpleaicv_pytorch_training_examples_amd.SimpleAICV.salient_object_detection import losses, models
+    from simpleaicv_pytorch_training_examples_amd.SimpleAICV.salient_object_detection.models import pfan_segmentation as pfan
+    from simpleaicv_pytorch_training_examples_amd.SimpleAICV.semantic_segmentation.models import pfan_semantic_segmentation as semseg
+    assert pfan.CPFE is semseg.CPFE and pfan.ConvBnActBlock is semseg.ConvBnActBlock                      # reused, not copied
+    assert pfan.ConvTransposeBnActBlock is semseg.ConvTransposeBnActBlock
+    assert len(pfan.__all__) == 13
+    for name in pfan.__all__:
+        model = models.__dict__[name]()
+        assert model.pred_conv.weight.shape == (1, 32, 3, 3) and model.head_route == 'fused', name
+        assert model.high_level_cpfe_3.conv_1_1.in_channels == model.backbone.out_channels[2], name
+    assert models.resnet18_pfan_segmentation(cpfe_planes=20).head_route == 'generic'
+    assert models.resnet18_pfan_segmentation(use_gradient_checkpoint=True).backbone.use_gradient_checkpoint is True
+    for name in ('BCELoss', 'OHEMBCELoss', 'BCEIouloss', 'BCEDiceLoss'):
+        assert isinstance(losses.__dict__[name](), torch.nn.Module)
+    assert losses.OHEMBCELoss(negative_ratio=3.0).negative_ratio == 3.0 and losses.BCEIouloss(smooth=1e-3).smooth == 1e-3
+    torch.manual_seed(0)
+    model = models.resnet18_pfan_segmentation(**fx['config'])
+    sd = model.state_dict()
+    assert [(k, tuple(v.shape)) for k, v in sorted(sd.items())] == [(k, tuple(s)) for k, s in fx['keys']]
+    assert set(fx['init_sample']) == {k for k, v in sd.items() if v.dtype.is_floating_point}
+    for k, ref in fx['init_sample'].items():
+        idx = torch.linspace(0, sd[k].numel() - 1, min(16, sd[k].numel())).long()
+        assert torch.equal(sd[k].flatten()[idx], ref), f'initial weights differ: {k}'
+
+
+def test_ohem_loss_is_the_reference_formula_on_cpu(fx):
+    """OHEMBCELoss is tensor code and runs anywhere: the reference value on the fixture's model output"""
+    from simpleaicv_pytorch_training_examples_amd.SimpleAICV.salient_object_detection.losses import OHEMBCELoss
+    _, mask = S.model_inputs(fx['input_shape'])
+    assert abs(float(OHEMBCELoss()(fx['out'], mask)) - fx['losses']['OHEMBCELoss']) <= 1e-6
+
+
+def test_collater_and_synthetic_dataset_contract():
+    from simpleaicv_pytorch_training_examples_amd.SimpleAICV.classification import common as cls_common
+    from simpleaicv_pytorch_training_examples_amd.SimpleAICV.salient_object_detection.common import (
+        SalientObjectDetectionSegmentationCollater, load_state_dict)
+    from simpleaicv_pytorch_training_examples_amd.SimpleAICV.salient_object_detection.datasets.syntheticdataset import (
+        SyntheticSalientObjectDetectionDataset)
+    assert load_state_dict is cls_common.load_state_dict
+    ds = SyntheticSalientObjectDetectionDataset(4, 24, 40, seed=0)
+    sample = ds[1]
+    assert len(ds) == 4 and sample['image'].shape == (24, 40, 3) and sample['image'].dtype == np.float32
+    assert sample['mask'].shape == (24, 40) and sample['mask'].dtype == np.float32
+    assert sample['mask'].min() >= 0. and sample['mask'].max() <= 1. and sample['mask'].max() > 0.5
+    assert ((sample['mask'] > 0) & (sample['mask'] < 1)).any()                  # soft edges
+    assert sample['size'].tolist() == [24, 40] and sample['size'].dtype == np.float32
+    assert np.array_equal(ds[1]['mask'], sample['mask']) and not np.array_equal(ds[2]['mask'], sample['mask'])
+    batch = SalientObjectDetectionSegmentationCollater(resize=48)([ds[0], ds[1]])
+    assert list(batch) == ['image', 'mask', 'size']
+    assert batch['image'].shape == (2, 3, 48, 48) and batch['image'].dtype == torch.float32
+    assert batch['mask'].shape == (2, 48, 48) and batch['mask'].dtype == torch.float32
+    assert isinstance(batch['size'], np.ndarray) and batch['size'].dtype == np.float32 and batch['size'].tolist() == [[24, 40], [24, 40]]
+    assert torch.equal(batch['image'][1, :, :24, :40], torch.from_numpy(sample['image']).permute(2, 0, 1))
+    assert torch.equal(batch['mask'][1, :24, :40], torch.from_numpy(sample['mask']))
+    assert float(batch['image'][:, :, 24:].abs().sum()) == 0 and float(batch['image'][:, :, :, 40:].abs().sum()) == 0
+    assert float(batch['mask'][:, 24:].abs().sum()) == 0 and float(batch['mask'][:, :, 40:].abs().sum()) == 0
+
+
+def test_benchmark_config_imports_with_the_shorteners(monkeypatch):
+    for k, v in dict(SAICV_SAL_TRAIN=8, SAICV_SAL_TEST=4, SAICV_SAL_BATCH=2, SAICV_SAL_WORKERS=0, SAICV_SAL_EPOCHS=2, SAICV_SAL_PRINT=1).items():
+        monkeypatch.setenv(k, str(v))
+    work_dir = os.path.join(ROOT, '06.salient_object_detection_training', 'resnet50_pfan_segmentation')
+    monkeypatch.syspath_prepend(ROOT)
+    configs = {}
+    for name in ('train_config', 'test_config'):
+        monkeypatch.syspath_prepend(work_dir)
+        monkeypatch.delitem(sys.modules, 'train_config', raising=False)
+        spec = importlib.util.spec_from_file_location(f'saicv_sal_{name}', os.path.join(work_dir, name + '.py'))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        configs[name] = mod.config
+    monkeypatch.delitem(sys.modules, 'train_config', raising=False)
+    c = configs['train_config']
+    assert c.network == 'resnet50_pfan_segmentation' and c.input_image_size == [1024, 1024]
+    assert list(c.train_criterion) == ['BCELoss', 'BCEIouloss'] and c.loss_ratio == {'BCELoss': 1.0, 'BCEIouloss': 1.0}
+    assert c.optimizer[0] == 'AdamW' and c.optimizer[1]['lr'] == 1e-4 and c.scheduler[0] == 'CosineLR'
+    assert c.thresh == [0.2] and c.squared_beta == 0.3 and c.save_model_metric == 'miou_average' and c.save_interval == 10
+    assert (len(c.train_dataset), len(c.val_dataset_list[0]), c.batch_size, c.num_workers, c.epochs, c.print_interval) == (8, 4, 2, 0, 2, 1)
+    assert len(c.val_dataset_name_list) == len(c.val_dataset_list) == 1 and c.use_amp is True
+    t = configs['test_config']
+    assert t.thresh == [0.2] and t.squared_beta == 0.3 and t.batch_size == 2 and len(t.val_dataset_list[0]) == 4
+    monkeypatch.delenv('SAICV_SAL_BATCH')
+    assert int(os.environ.get('SAICV_SAL_BATCH', 64)) == 64                      # the reference's global batch is the default
