@@ -170,6 +170,24 @@ typedef struct saicv_dgrad_fuse {
 int saicv_conv2d_dgrad_stat_rows(const saicv_conv_desc* d);
 int saicv_conv2d_dgrad_fused(const saicv_conv_desc* d, const void* dy, const void* wd, const saicv_dgrad_fuse* f, void* dx,
                              void* stream);
+/* ---- backward of a bottleneck block's third (1 x 1, stride 1) convolution behind its BatchNorm + residual + ReLU join, one stream:
+ * the BatchNorm-backward apply pass, the data gradient and the weight gradient in ONE kernel; dy (the gradient of the convolution
+ * output) is never stored.  bf16, (CO, CI) = (256, 64) or (512, 128).
+ *   dz [M][CO], relu_mask (one byte per 8 channels), y [M][CO] = the convolution output before BatchNorm; gamma / mean / invstd [CO];
+ *   part_g / part_gx: `rows` rows of the join's backward sums (saicv_conv2d_dgrad_fused); dgamma / dbeta written (accumulate: added);
+ *   ws: saicv_c3_bwd_stream_ws_floats(M, CO, CI) floats (asked in the reduction mode of the launch); x [M][CI] the convolution's input, wd [CI][CO] its data-gradient weights; dx [M][CI] written;
+ *   dw [CO][CI] fp32 ACCUMULATED into (ordered partials + fold in both reduction modes);
+ *   f: NULL, or bn_y / bn_mask / bn_mean / bn_invstd / part_g / part_gx / part_rows as saicv_conv2d_dgrad_fused takes them
+ *   (addend must be NULL); with part_rows == 0 the sums are saicv_c3_bwd_stream_rows(M, CO, CI) rows, one per workgroup.
+ * saicv_c3_bwd_stream_ok: rows of the launch (non-zero) when the layer takes this route -- a pure function of its arguments,
+ * SAICV_C3_BWD_STREAM (default 1) and SAICV_C3_BWD_MIN_ROWS (default 65536), both read per call; the launch itself ignores them. */
+int saicv_c3_bwd_stream_ok(int dtype, int M, int CO, int CI);
+int saicv_c3_bwd_stream_rows(int M, int CO, int CI);
+size_t saicv_c3_bwd_stream_ws_floats(int M, int CO, int CI);
+int saicv_c3_bwd_stream(int dtype, const void* dz, const void* relu_mask, const void* y, const float* gamma, const float* mean,
+                        const float* invstd, const float* part_g, const float* part_gx, int rows, float* dgamma, float* dbeta,
+                        int accumulate, float* ws, const void* x, const void* wd, const saicv_dgrad_fuse* f, void* dx, float* dw,
+                        int M, int CO, int CI, void* stream);
 /* ---- launch plan query ------------------------------------------------------------------
  * What the convolution / linear entry points above decide before they launch, as a host-side function of the problem
  * alone: no tensors, no stream, nothing reaches the GPU.  It asks the same plan functions the launches ask and reads the

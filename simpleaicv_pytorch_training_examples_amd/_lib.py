@@ -112,6 +112,10 @@ SIGNATURES = {
     'saicv_conv2d_dgrad_add': (c_int, [_PD, _P, _P, _P, _P, _P]),
     'saicv_conv2d_dgrad_stat_rows': (c_int, [_PD]),
     'saicv_conv2d_dgrad_fused': (c_int, [_PD, _P, _P, _PF, _P, _P]),
+    'saicv_c3_bwd_stream_ok': (c_int, [c_int, c_int, c_int, c_int]),
+    'saicv_c3_bwd_stream_rows': (c_int, [c_int, c_int, c_int]),
+    'saicv_c3_bwd_stream_ws_floats': (c_size_t, [c_int, c_int, c_int]),
+    'saicv_c3_bwd_stream': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, c_int, _P, _P, _P, _PF, _P, _P, c_int, c_int, c_int, _P]),
     'saicv_igemm_plan': (c_int, [POINTER(PlanQuery), POINTER(Plan)]),
     'saicv_conv2d_fwd_stats': (c_int, [_PD, _P, _P, _P, _P, _P, c_int, _P]),
     'saicv_bn_act_fwd_stats': (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_double, _P, _P, _P, _P, c_double, c_double, _P, _P, _P,

@@ -661,6 +661,19 @@ int bn_bwd_from_partials(int dtype, const void* dz, const void* relu_mask, const
                            part_g, part_gx, rows);
 }
 
+// the finalize launch of bn_bwd_t on its own (c3bwd.hip applies the coefficients inside the fused stream): ws = [2][32][C] second
+// stage + [3][C] coefficients
+int bn_bwd_coeffs(const float* part_g, const float* part_gx, int rows, int C, size_t M, const float* gamma, const float* mean,
+                  const float* invstd, float* dgamma, float* dbeta, int accumulate, float* ws, hipStream_t st) {
+    SAICV_REQUIRE(part_g != nullptr && part_gx != nullptr && rows > 0 && ws != nullptr, "bn_bwd_coeffs: partial sums missing");
+    const float* a = part_g; const float* b = part_gx;
+    float* coef = ws + (size_t)64 * C;
+    const int P = reduce_partials(a, b, rows, C, ws, st);
+    hipLaunchKernelGGL(P <= 32 ? bn_finalize_bwd_kernel<4> : bn_finalize_bwd_kernel<16>, dim3((C + 63) / 64), dim3(P <= 32 ? 256 : 1024), 0, st, a, b, P, C,
+                       (float)M, gamma, mean, invstd, dgamma, dbeta, coef, coef + C, coef + 2 * C, accumulate);
+    return check_launch("bn_bwd_coeffs");
+}
+
 int bn_bwd(int dtype, const void* dz, const void* z, const void* relu_mask, const void* y, const float* gamma,
            const float* mean, const float* invstd, void* dy, void* dres, float* dgamma, float* dbeta,
            size_t M, int C, int relu, int accumulate, float* ws, hipStream_t st) {

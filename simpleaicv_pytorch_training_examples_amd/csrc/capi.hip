@@ -267,6 +267,31 @@ int saicv_conv2d_dgrad_fused(const saicv_conv_desc* d, const void* dy, const voi
                     d->R, d->S, d->stride, d->pad, M, d->C, d->R * d->S * d->K, d->C, 0, S(stream),
                     (f->addend || f->bn_y) ? &ex : nullptr);
 }
+// BatchNorm-backward apply + data gradient + weight gradient of a bottleneck's third 1 x 1 convolution as one stream (c3bwd.hip)
+int saicv_c3_bwd_stream_ok(int dtype, int M, int CO, int CI) { return c3_bwd_stream_blocks(dtype, M, CO, CI); }
+int saicv_c3_bwd_stream_rows(int M, int CO, int CI) { return c3_bwd_stream_rows(M, CO, CI); }
+size_t saicv_c3_bwd_stream_ws_floats(int M, int CO, int CI) { return c3_bwd_stream_ws_floats(M, CO, CI); }
+int saicv_c3_bwd_stream(int dtype, const void* dz, const void* relu_mask, const void* y, const float* gamma, const float* mean,
+                        const float* invstd, const float* part_g, const float* part_gx, int rows, float* dgamma, float* dbeta,
+                        int accumulate, float* ws, const void* x, const void* wd, const saicv_dgrad_fuse* f, void* dx, float* dw,
+                        int M, int CO, int CI, void* stream) {
+    SAICV_REQUIRE(dtype == SAICV_BF16, "saicv_c3_bwd_stream: bf16 only (dtype %d)", dtype);
+    SAICV_REQUIRE(c3_bwd_stream_rows(M, CO, CI) > 0, "saicv_c3_bwd_stream: no form for M = %d, Cout = %d, Cin = %d", M, CO, CI);
+    SAICV_REQUIRE(mean && invstd && ws, "saicv_c3_bwd_stream: statistics / workspace missing");
+    SAICV_REQUIRE(!f || (!f->addend && !f->addend_gate), "saicv_c3_bwd_stream: no addend form");
+    if (bn_bwd_coeffs(part_g, part_gx, rows, CO, (size_t)M, gamma, mean, invstd, dgamma, dbeta, accumulate, ws, S(stream)) != 0) return -1;
+    EpiExtra ex;
+    if (f && f->bn_y) {
+        ex.bs_y = f->bn_y;
+        ex.bs_mask = static_cast<const uint8_t*>(f->bn_mask);
+        ex.bs_mean = f->bn_mean;
+        ex.bs_invstd = f->bn_invstd;
+        ex.bs_g = f->part_g;
+        ex.bs_gx = f->part_gx;
+    }
+    return c3_bwd_stream(M, CO, CI, dz, y, relu_mask, ws + (size_t)64 * CO, x, wd, dx, dw, (f && f->bn_y) ? &ex : nullptr,
+                         f ? f->part_rows : 0, ws + (size_t)67 * CO, S(stream));
+}
 int saicv_igemm_plan(const saicv_plan_query* q, saicv_plan* plan) {
     if (!q || !plan) { set_error("saicv_igemm_plan: null argument"); return -1; }
     SAICV_REQUIRE(q->op >= SAICV_PLAN_CONV_FWD && q->op <= SAICV_PLAN_LINEAR_WGRAD, "saicv_igemm_plan: bad op %d", q->op);

@@ -52,6 +52,18 @@ int pw3_stream_blocks(int dtype, int M, int Nn, int Kd);
 int pw3_stream(int mode, int M, int H, int W, const void* src, const void* wgt, void* out, float* stat_sum, float* stat_sq,
                int stat_atomic_rows, const EpiExtra* ex, int stream_out, int blocks, hipStream_t st);
 
+// c3bwd.hip: BatchNorm-backward apply + data gradient + weight gradient of a bottleneck's third convolution as one stream (dy never
+// stored); blocks = rows of partial BatchNorm-backward sums (0: not eligible).  coef = [3][CO] of bn_bwd_coeffs.
+int c3_bwd_stream_blocks(int dtype, int M, int CO, int CI);
+int c3_bwd_stream_rows(int M, int CO, int CI);
+int c3_bwd_stream(int M, int CO, int CI, const void* dz, const void* y, const void* mask, const float* coef, const void* x,
+                  const void* wd, void* dx, float* dw, const EpiExtra* ex, int bs_rows, float* part_ws, hipStream_t st);
+size_t c3_bwd_stream_ws_floats(int M, int CO, int CI);
+// bn.hip: the finalize step of BatchNorm backward alone: `rows` rows of partial sums -> dgamma, dbeta and the coefficients
+// ca, cb, cc of dy = ca * g + cb * y + cc at ws + 64 * C (ws: 67 * C floats)
+int bn_bwd_coeffs(const float* part_g, const float* part_gx, int rows, int C, size_t M, const float* gamma, const float* mean,
+                  const float* invstd, float* dgamma, float* dbeta, int accumulate, float* ws, hipStream_t st);
+
 // sam.hip
 int window_partition(int dtype, const void* x, void* out, int B, int H, int W, int C, int ws, hipStream_t st);
 int window_unpartition(int dtype, const void* win, const void* addend, void* out, int B, int H, int W, int C, int ws,

@@ -877,6 +877,77 @@ def _pooled_bn_backward(ctx, st, dz, gamma, y, idx, mean, invstd):
     return (dy, None, None, None) if direct_bn else (dy, None, dgamma, dbeta)
 
 
+def _c3_fused_backward(ctx, st, dz, dz_is_given, gate_in, dskip, x, weight, gamma, y, mask, mean, invstd):
+    """The whole backward of a bottleneck block's third convolution (1 x 1, stride 1, behind BatchNorm + residual + ReLU) as one
+    stream, csrc/c3bwd.hip: finalize launch (coefficients, dgamma, dbeta), then BatchNorm-backward apply + data gradient + weight
+    gradient in one kernel -- dy is never allocated -- then the fold.  -> ConvBnActFn.backward's return tuple, or None when the
+    node does not qualify (everything else takes the three-kernel path untouched): bf16; the shortcut gradient leaves gated (dres
+    is dz, nothing to write); the backward sums came from the data gradient that produced dz; input and weight both want gradients."""
+    stride, pad, relu, has_res, training, d, wd = ctx.cfg
+    dt = y.dtype
+    if not (BN_FUSE and dt == torch.bfloat16 and relu and has_res and mask is not None and gate_in is None and dskip is None
+            and dz_is_given and ctx.s2d is None and (d.R, d.S, d.stride, d.pad) == (1, 1, 1, 0)
+            and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and (ctx.gated_res or not ctx.needs_input_grad[4])):
+        return None
+    link = ctx.link
+    if not (link is not None and link.part is not None and link.dx is not None and dz.data_ptr() == link.dx.data_ptr()
+            and dz.shape == link.dx.shape and dz._version == link.dx_version):
+        return None
+    n, k, oh, ow = y.shape
+    c = x.shape[1]
+    M = n * oh * ow
+    if c != weight.shape[1] or tuple(x.shape) != (n, c, oh, ow) or x.dtype != dt:
+        return None
+    L, dev = lib(), y.device
+    rows = L.saicv_c3_bwd_stream_ok(dtype_code(dt), M, k, c)
+    if rows <= 0:
+        return None
+    dres = None
+    if ctx.needs_input_grad[4]:
+        dres = dz                           # the masked copy is not written: the consumer gets dz and the mask
+        dres._saicv_gate = mask
+        dres._saicv_gate_version = dres._version
+        _GateLedger.hand_out()
+    dgamma, dbeta, direct_bn = _bn_grad_buffers(gamma, ctx.beta_ref, k, dev)
+    ws = torch.empty(L.saicv_c3_bwd_stream_ws_floats(M, k, c), dtype=torch.float32, device=dev)
+    if wd is None:
+        _, wd = packed_weight(weight, dt, c, True, d.K)
+    in_link = ctx.in_link
+    fuse = None
+    if in_link is not None:                 # the backward sums of the BatchNorm(+ReLU) node that produced x, over the stored dx
+        fuse = _lib.DgradFuse()
+        in_link.inline = BN_INLINE and c <= 2048
+        if in_link.inline:
+            prow = _stat_rows(rows)
+            part = _ZeroPool.take(2 * prow * c, dev).view(2, prow, c)
+            fuse.part_rows = prow
+        else:
+            prow = rows
+            part = torch.empty((2, rows, c), dtype=torch.float32, device=dev)
+        fuse.bn_y, fuse.bn_mask = ptr(in_link.y), ptr(in_link.mask)
+        fuse.bn_mean, fuse.bn_invstd = ptr(in_link.mean), ptr(in_link.invstd)
+        fuse.part_g, fuse.part_gx = ptr(part[0]), ptr(part[1])
+        in_link.part, in_link.rows = part, prow
+    dx = _empty_nhwc(n, c, oh, ow, dt, dev)
+    gw = _arena_grad(weight)
+    direct = (gw is not None and d.K == weight.shape[0] and weight.is_contiguous(memory_format=torch.channels_last))
+    dw = gw if direct else torch.zeros((k, 1, 1, c), dtype=torch.float32, device=dev)
+    t0 = KernelTimer.begin('c3_bwd_stream')
+    check(L.saicv_c3_bwd_stream(dtype_code(dt), ptr(dz), ptr(mask), ptr(y), ptr(gamma), ptr(mean), ptr(invstd), ptr(link.part[0]),
+                                ptr(link.part[1]), link.rows, ptr(dgamma), ptr(dbeta), int(direct_bn), ptr(ws), ptr(x), ptr(wd),
+                                ctypes.byref(fuse) if fuse is not None else None, ptr(dx), ptr(dw), M, k, c, st), 'c3_bwd_stream')
+    # both products; dz, y, x, the c2 node's y and dx: 2.75 passes over an [M][k] tensor at c = k / 4
+    KernelTimer.end(t0, 'c3_bwd_stream', 2 * 2.0 * M * k * c, 2.75 * M * k * y.element_size())
+    link.part = link.dx = None
+    if in_link is not None:
+        in_link.dx, in_link.dx_version = dx, dx._version
+    dwt = None if direct else _weight_grad(dw, weight, c)
+    if direct_bn:
+        dgamma = dbeta = None
+    return (dx, dwt, dgamma if ctx.needs_input_grad[2] else None, dbeta if ctx.needs_input_grad[3] else None, dres,
+            None, None, None, None, None, None, None)
+
+
 class ConvBnActFn(torch.autograd.Function):
     """conv -> [BatchNorm2d (train: batch stats, eval: running stats)] -> [+residual] -> [ReLU].
 
@@ -922,6 +993,10 @@ class ConvBnActFn(torch.autograd.Function):
         gate_in = _take_gate(dz)          # dz is a shortcut gradient still waiting for the ReLU mask of the block's tail
         dz0 = dz
         dz = _nhwc(dz, dt)
+        if ctx.pool is None:
+            fused = _c3_fused_backward(ctx, st, dz, dz is dz0, gate_in, dskip, x, weight, gamma, y, mask, mean, invstd)
+            if fused is not None:
+                return fused
         if ctx.pool is not None:
             dy, dres, dgamma, dbeta = _pooled_bn_backward(ctx, st, dz, gamma, y, mask, mean, invstd)
         else:
