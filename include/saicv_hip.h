@@ -507,6 +507,54 @@ int saicv_binary_seg_stats_fwd(const float* prob, const float* label, int B, siz
 int saicv_binary_seg_stats_bwd(const float* prob, const float* label, const float* gstats, int B, size_t P, float* dprob,
                                void* stream);
 
+/* ---- human matting (human_matting/losses.py:21-287 the seven losses; human_matting/models/pfan_matting.py:434-454
+ *      collaborative_matting).  All maps fp32; ph = clamp(p, float32(1e-4), float32(1 - 1e-4)); every sum is an ordered two-stage
+ *      sum through `partial` (no atomics); every backward reads dL/dsums from device memory and is exactly 0 where p lies outside
+ *      the clamp (bounds inclusive). ---- */
+/* floats of `partial` for the pixel kernels below (B samples of P pixels) */
+size_t saicv_matting_ws_floats(int B, size_t P);
+/* global_pred: three probabilities per pixel, element (b, c, i) at global_pred[b * sb + c * sc + i * sp] (NCHW: 3P, P, 1;
+ * channels-last: 3P, 1, 3); trimap [B][P] with class 255 -> 2, else anything > 2 -> 1, else (long)t.  stats [B][2] =
+ * (sum over pixels and channels of the bce against the one-hot class,
+ *  sum over pixels of 1 - (ph_k + smooth) / (ph_0 + ph_1 + ph_2 + 1 - ph_k + smooth)). */
+int saicv_trimap_stats_fwd(const float* global_pred, long sb, long sc, long sp, const float* trimap, int B, size_t P, float smooth,
+                           float* partial, float* stats, void* stream);
+/* dglobal (the strides of global_pred) from gstats [B][2] = dL/dstats */
+int saicv_trimap_stats_bwd(const float* global_pred, long sb, long sc, long sp, const float* trimap, const float* gstats, int B,
+                           size_t P, float smooth, float* dglobal, void* stream);
+/* pred, alpha [B][P], trimap [B][P] or NULL: sums [B][2] = (sum sqrt(((ph - alpha) w)^2 + 1e-12), sum w), w = [trimap == 128]
+ * or 1; a pixel with w = 0 still adds sqrt(1e-12).  Backward: dpred from gsums [B][2] (only gsums[b][0] is read). */
+int saicv_alpha_l1_fwd(const float* pred, const float* alpha, const float* trimap, int B, size_t P, float* partial, float* sums,
+                       void* stream);
+int saicv_alpha_l1_bwd(const float* pred, const float* alpha, const float* trimap, const float* gsums, int B, size_t P, float* dpred,
+                       void* stream);
+/* pred [B][P]; fg, bg, image [B][3][P]: sums [B] = sum over pixels and channels of sqrt((ph fg + (1 - ph) bg - image)^2 + 1e-12);
+ * the gradient goes to pred only */
+int saicv_composition_l1_fwd(const float* pred, const float* fg, const float* bg, const float* image, int B, size_t P,
+                             float* partial, float* sums, void* stream);
+int saicv_composition_l1_bwd(const float* pred, const float* fg, const float* bg, const float* image, const float* gsums, int B,
+                             size_t P, float* dpred, void* stream);
+/* fused [B][P] = local_pred [argmax == 1] + [argmax == 2], argmax = the FIRST maximum of the three global probabilities
+ * (torch.max's tie rule); dlocal = dfused [argmax == 1]; global_pred receives no gradient */
+int saicv_matting_fuse_fwd(const float* global_pred, long sb, long sc, long sp, const float* local_pred, int B, size_t P,
+                           float* fused, void* stream);
+int saicv_matting_fuse_bwd(const float* global_pred, long sb, long sc, long sp, const float* dfused, int B, size_t P, float* dlocal,
+                           void* stream);
+/* One level of the Laplacian pyramid of LocalLaplacianLoss / FusionLaplacianLoss.  cur [B][h][w] (any h, w >= 1); table: the 25
+ * weights of G, row-major, read on the host and passed to the kernel by value; G * cur uses replicate padding 2.
+ * sum_e [B] = sum |cur - G * cur|; next [B][h / 2][w / 2] = avg_pool2(G * cur) (an odd last row / column is dropped);
+ * sum_next [B] (or NULL) = sum |next|.  level0 != 0: cur = (clamp(src) - alpha) * w is formed while loading, w = [trimap == 128]
+ * or 1 (trimap NULL).  partial: saicv_lap_level_ws_floats floats. */
+size_t saicv_lap_level_ws_floats(int B, int h, int w);
+int saicv_lap_level_fwd(const float* src, const float* alpha, const float* trimap, int level0, int B, int h, int w,
+                        const float* table, float* next, float* partial, float* sum_e, float* sum_next, void* stream);
+/* The exact adjoint: gcur = gs sign(e) + G^T (P^T gnext - gs sign(e)), e = cur - G * cur recomputed, sign(0) = 0; gs [B] =
+ * dL/dsum_e.  gnext [B][h / 2][w / 2] = dL/dnext, or with topcur (the saved next map) and gtop [B] = dL/dsum_next:
+ * gnext = gtop sign(topcur).  G^T is the adjoint of replicate padding.  level0: gcur is dL/dsrc (times w, 0 outside the clamp). */
+int saicv_lap_level_bwd(const float* src, const float* alpha, const float* trimap, int level0, int B, int h, int w,
+                        const float* table, const float* gnext, const float* topcur, const float* gs, const float* gtop, float* gcur,
+                        void* stream);
+
 /* Streaming attention (any Nq / Nk, head dim 32 or 64, separate q / k / v with strides).
  * Replaces SAM Attention.forward + add_decomposed_rel_pos (reference interactive_segmentation/models/
  * segment_anything/image_encoder.py:116-184) and DETR's nn.MultiheadAttention calls with a float

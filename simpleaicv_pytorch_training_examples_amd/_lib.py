@@ -240,6 +240,18 @@ SIGNATURES = {
     'saicv_binary_seg_stats_ws_floats': (c_size_t, [c_int, c_size_t]),
     'saicv_binary_seg_stats_fwd': (c_int, [_P, _P, c_int, c_size_t, _P, _P, _P]),
     'saicv_binary_seg_stats_bwd': (c_int, [_P, _P, _P, c_int, c_size_t, _P, _P]),
+    'saicv_matting_ws_floats': (c_size_t, [c_int, c_size_t]),
+    'saicv_trimap_stats_fwd': (c_int, [_P, c_long, c_long, c_long, _P, c_int, c_size_t, ctypes.c_float, _P, _P, _P]),
+    'saicv_trimap_stats_bwd': (c_int, [_P, c_long, c_long, c_long, _P, _P, c_int, c_size_t, ctypes.c_float, _P, _P]),
+    'saicv_alpha_l1_fwd': (c_int, [_P, _P, _P, c_int, c_size_t, _P, _P, _P]),
+    'saicv_alpha_l1_bwd': (c_int, [_P, _P, _P, _P, c_int, c_size_t, _P, _P]),
+    'saicv_composition_l1_fwd': (c_int, [_P, _P, _P, _P, c_int, c_size_t, _P, _P, _P]),
+    'saicv_composition_l1_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_size_t, _P, _P]),
+    'saicv_matting_fuse_fwd': (c_int, [_P, c_long, c_long, c_long, _P, c_int, c_size_t, _P, _P]),
+    'saicv_matting_fuse_bwd': (c_int, [_P, c_long, c_long, c_long, _P, c_int, c_size_t, _P, _P]),
+    'saicv_lap_level_ws_floats': (c_size_t, [c_int] * 3),
+    'saicv_lap_level_fwd': (c_int, [_P, _P, _P] + [c_int] * 4 + [POINTER(ctypes.c_float)] + [_P] * 5),
+    'saicv_lap_level_bwd': (c_int, [_P, _P, _P] + [c_int] * 4 + [POINTER(ctypes.c_float)] + [_P] * 6),
     'saicv_attention_stream_fwd': (c_int, [c_int, c_int, _PA, _P]),
     'saicv_attention_stream_bwd': (c_int, [c_int, c_int, _PA, _P]),
 }

@@ -586,6 +586,51 @@ int saicv_binary_seg_stats_bwd(const float* prob, const float* label, const floa
                                void* stream) {
     return binary_seg_stats_bwd(prob, label, gstats, B, P, dprob, S(stream));
 }
+size_t saicv_matting_ws_floats(int B, size_t P) { return matting_ws_floats(B, P); }
+int saicv_trimap_stats_fwd(const float* global_pred, long sb, long sc, long sp, const float* trimap, int B, size_t P, float smooth,
+                           float* partial, float* stats, void* stream) {
+    return trimap_stats_fwd(global_pred, sb, sc, sp, trimap, B, P, smooth, partial, stats, S(stream));
+}
+int saicv_trimap_stats_bwd(const float* global_pred, long sb, long sc, long sp, const float* trimap, const float* gstats, int B,
+                           size_t P, float smooth, float* dglobal, void* stream) {
+    return trimap_stats_bwd(global_pred, sb, sc, sp, trimap, gstats, B, P, smooth, dglobal, S(stream));
+}
+int saicv_alpha_l1_fwd(const float* pred, const float* alpha, const float* trimap, int B, size_t P, float* partial, float* sums,
+                       void* stream) {
+    return alpha_l1_fwd(pred, alpha, trimap, B, P, partial, sums, S(stream));
+}
+int saicv_alpha_l1_bwd(const float* pred, const float* alpha, const float* trimap, const float* gsums, int B, size_t P, float* dpred,
+                       void* stream) {
+    return alpha_l1_bwd(pred, alpha, trimap, gsums, B, P, dpred, S(stream));
+}
+int saicv_composition_l1_fwd(const float* pred, const float* fg, const float* bg, const float* image, int B, size_t P,
+                             float* partial, float* sums, void* stream) {
+    return composition_l1_fwd(pred, fg, bg, image, B, P, partial, sums, S(stream));
+}
+int saicv_composition_l1_bwd(const float* pred, const float* fg, const float* bg, const float* image, const float* gsums, int B,
+                             size_t P, float* dpred, void* stream) {
+    return composition_l1_bwd(pred, fg, bg, image, gsums, B, P, dpred, S(stream));
+}
+int saicv_matting_fuse_fwd(const float* global_pred, long sb, long sc, long sp, const float* local_pred, int B, size_t P,
+                           float* fused, void* stream) {
+    return matting_fuse_fwd(global_pred, sb, sc, sp, local_pred, B, P, fused, S(stream));
+}
+int saicv_matting_fuse_bwd(const float* global_pred, long sb, long sc, long sp, const float* dfused, int B, size_t P, float* dlocal,
+                           void* stream) {
+    return matting_fuse_bwd(global_pred, sb, sc, sp, dfused, B, P, dlocal, S(stream));
+}
+size_t saicv_lap_level_ws_floats(int B, int h, int w) { return lap_level_ws_floats(B, h, w); }
+int saicv_lap_level_fwd(const float* src, const float* alpha, const float* trimap, int level0, int B, int h, int w,
+                        const float* table, float* next, float* partial, float* sum_e, float* sum_next, void* stream) {
+    if (!table) { set_error("lap_level_fwd: null weight table"); return -1; }
+    return lap_level_fwd(src, alpha, trimap, level0, B, h, w, table, next, partial, sum_e, sum_next, S(stream));
+}
+int saicv_lap_level_bwd(const float* src, const float* alpha, const float* trimap, int level0, int B, int h, int w,
+                        const float* table, const float* gnext, const float* topcur, const float* gs, const float* gtop, float* gcur,
+                        void* stream) {
+    if (!table) { set_error("lap_level_bwd: null weight table"); return -1; }
+    return lap_level_bwd(src, alpha, trimap, level0, B, h, w, table, gnext, topcur, gs, gtop, gcur, S(stream));
+}
 int saicv_attention_stream_fwd(int dtype, int D, const saicv_attn_desc* desc, void* stream) {
     if (!desc) { set_error("attention_stream: null descriptor"); return -1; }
     return attention_stream(dtype, D, 0, desc, S(stream));

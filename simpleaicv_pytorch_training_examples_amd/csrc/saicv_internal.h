@@ -107,6 +107,27 @@ int conv3x3_c1_bwd(int dtype, const void* x, const float* weight, long wsc, long
 size_t binary_seg_stats_ws_floats(int B, size_t P);
 int binary_seg_stats_fwd(const float* prob, const float* label, int B, size_t P, float* partial, float* stats, hipStream_t st);
 int binary_seg_stats_bwd(const float* prob, const float* label, const float* gstats, int B, size_t P, float* dprob, hipStream_t st);
+// matting.hip
+size_t matting_ws_floats(int B, size_t P);
+int trimap_stats_fwd(const float* gp, long sb, long sc, long sp, const float* trimap, int B, size_t P, float smooth, float* partial,
+                     float* stats, hipStream_t st);
+int trimap_stats_bwd(const float* gp, long sb, long sc, long sp, const float* trimap, const float* gstats, int B, size_t P,
+                     float smooth, float* dgp, hipStream_t st);
+int alpha_l1_fwd(const float* pred, const float* alpha, const float* trimap, int B, size_t P, float* partial, float* sums,
+                 hipStream_t st);
+int alpha_l1_bwd(const float* pred, const float* alpha, const float* trimap, const float* gsums, int B, size_t P, float* dpred,
+                 hipStream_t st);
+int composition_l1_fwd(const float* pred, const float* fg, const float* bg, const float* image, int B, size_t P, float* partial,
+                       float* sums, hipStream_t st);
+int composition_l1_bwd(const float* pred, const float* fg, const float* bg, const float* image, const float* gsums, int B, size_t P,
+                       float* dpred, hipStream_t st);
+int matting_fuse_fwd(const float* gp, long sb, long sc, long sp, const float* local, int B, size_t P, float* fused, hipStream_t st);
+int matting_fuse_bwd(const float* gp, long sb, long sc, long sp, const float* dfused, int B, size_t P, float* dlocal, hipStream_t st);
+size_t lap_level_ws_floats(int B, int h, int w);
+int lap_level_fwd(const float* src, const float* alpha, const float* trimap, int level0, int B, int h, int w, const float* table,
+                  float* next, float* partial, float* sum_e, float* sum_next, hipStream_t st);
+int lap_level_bwd(const float* src, const float* alpha, const float* trimap, int level0, int B, int h, int w, const float* table,
+                  const float* gnext, const float* topcur, const float* gs, const float* gtop, float* gcur, hipStream_t st);
 // attn_stream.hip: which = 0 forward, 1 dQ pass, 2 dK/dV pass; desc = const saicv_attn_desc*
 int attention_stream(int dtype, int D, int which, const void* desc, hipStream_t st);
 

@@ -1897,6 +1897,353 @@ def binary_seg_stats(prob, label):
     return stats
 
 
+# ------------------------------------------------------------------------------ human matting (csrc/matting.hip)
+LAP_LEVELS = 5
+LAP_MIN_SIDE = 32
+_lap_default = [None]
+
+
+def laplacian_gauss_table():
+    """the 25 weights of the reference's build_gauss_kernel(size=5, sigma=1.0) (SimpleAICV/human_matting/losses.py:149-159) by the
+    same numpy formula in float32: the SUM of the two axis Gaussians over the grid, normalised -- K[i, j] = (g_i + g_j) / S, not
+    the product Gaussian.  -> a tuple of 25 floats, row-major"""
+    if _lap_default[0] is None:
+        import numpy as np
+        size, sigma = 5, 1.0
+        grid = np.float32(np.mgrid[0:size, 0:size].T)
+        kernel = np.sum(np.exp(-((grid - size // 2) ** 2) / (2 * sigma ** 2)), axis=2)
+        kernel /= np.sum(kernel)
+        _lap_default[0] = tuple(float(v) for v in np.float32(kernel).reshape(-1))
+    return _lap_default[0]
+
+
+def _f32c(t):
+    return t if t is None or (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+def _tri_layout(gp):
+    """global_pred [B, 3, H, W] -> (fp32 tensor, (sb, sc, sp)): NCHW-contiguous and channels-last memory are read in place, anything
+    else through a contiguous copy"""
+    if gp.dim() != 4 or gp.shape[1] != 3:
+        raise ValueError(f'global_pred must be [B, 3, H, W], got {tuple(gp.shape)}')
+    if gp.dtype != torch.float32:
+        gp = gp.float()
+    if not (gp.is_contiguous() or gp.is_contiguous(memory_format=torch.channels_last)):
+        gp = gp.contiguous()
+    b, _, h, w = gp.shape
+    sp = gp.stride(3) if w > 1 else (gp.stride(2) if h > 1 else 1)
+    if h > 1 and w > 1 and gp.stride(2) != w * gp.stride(3):
+        gp = gp.contiguous()
+        sp = 1
+    return gp, (gp.stride(0) if b > 1 else 3 * h * w, gp.stride(1), sp)
+
+
+class TrimapStatsFn(torch.autograd.Function):
+    """global_pred [B, 3, H, W] probabilities, trimap [B, H, W] -> [B, 2] = (sum of the 3-channel bce against the one-hot class, sum
+    of the per-pixel IoU term): what GlobalTrimapCELoss and GloabelTrimapIouLoss (SimpleAICV/human_matting/losses.py:21-88) read of
+    the maps.  One read each way; the backward takes dL/dstats on the device and is exactly 0 outside the clamp."""
+
+    @staticmethod
+    def forward(ctx, gp, trimap, smooth):
+        gp, (sb, sc, sp) = _tri_layout(gp)
+        b, p = gp.shape[0], gp.shape[2] * gp.shape[3]
+        L, dev = lib(), gp.device
+        stats = torch.empty((b, 2), dtype=torch.float32, device=dev)
+        partial = torch.empty(L.saicv_matting_ws_floats(b, p), dtype=torch.float32, device=dev)
+        t0 = KernelTimer.begin('trimap_stats')
+        check(L.saicv_trimap_stats_fwd(ptr(gp), sb, sc, sp, ptr(trimap), b, p, float(smooth), ptr(partial), ptr(stats), stream()),
+              'trimap_stats_fwd')
+        KernelTimer.end(t0, 'trimap_stats', 0, 16 * b * p)
+        ctx.save_for_backward(gp, trimap)
+        ctx.layout, ctx.smooth = (sb, sc, sp), float(smooth)
+        return stats
+
+    @staticmethod
+    def backward(ctx, g):
+        gp, trimap = ctx.saved_tensors
+        b, p = gp.shape[0], gp.shape[2] * gp.shape[3]
+        sb, sc, sp = ctx.layout
+        g = g.float().contiguous()
+        dgp = torch.empty_like(gp)
+        if dgp.stride() != gp.stride():
+            raise RuntimeError('trimap_stats: the gradient did not take the layout of global_pred')
+        t0 = KernelTimer.begin('trimap_stats')
+        check(lib().saicv_trimap_stats_bwd(ptr(gp), sb, sc, sp, ptr(trimap), ptr(g), b, p, ctx.smooth, ptr(dgp), stream()),
+              'trimap_stats_bwd')
+        KernelTimer.end(t0, 'trimap_stats', 0, 28 * b * p)
+        return dgp, None, None
+
+
+def trimap_stats(global_pred, trimap, smooth=1e-4):
+    """-> [B, 2] fp32: per sample (sum bce, sum of 1 - (ph_k + smooth) / (sum ph + 1 - ph_k + smooth)); class k of a trimap value:
+    255 -> 2, else anything > 2 -> 1, else its integer part (the reference's order of rewrites)"""
+    require_gpu(global_pred, trimap)
+    trimap = _f32c(trimap)
+    if trimap.numel() != global_pred.numel() // 3:
+        raise ValueError(f'trimap_stats: global_pred {tuple(global_pred.shape)} and trimap {tuple(trimap.shape)} do not match')
+    return TrimapStatsFn.apply(global_pred, trimap, smooth)
+
+
+class AlphaL1Fn(torch.autograd.Function):
+    """pred, alpha [B, P], trimap [B, P] or None -> [B, 2] = (sum sqrt(((ph - alpha) w)^2 + 1e-12), sum w), w = [trimap == 128] or 1:
+    LocalAlphaLoss / FusionAlphaLoss (SimpleAICV/human_matting/losses.py:91-114, :183-203)"""
+
+    @staticmethod
+    def forward(ctx, pred, alpha, trimap):
+        b, p = pred.shape
+        L, dev = lib(), pred.device
+        sums = torch.empty((b, 2), dtype=torch.float32, device=dev)
+        partial = torch.empty(L.saicv_matting_ws_floats(b, p), dtype=torch.float32, device=dev)
+        t0 = KernelTimer.begin('alpha_l1')
+        check(L.saicv_alpha_l1_fwd(ptr(pred), ptr(alpha), ptr(trimap), b, p, ptr(partial), ptr(sums), stream()), 'alpha_l1_fwd')
+        KernelTimer.end(t0, 'alpha_l1', 0, (8 if trimap is None else 12) * b * p)
+        ctx.save_for_backward(pred, alpha, trimap)
+        return sums
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, alpha, trimap = ctx.saved_tensors
+        b, p = pred.shape
+        g = g.float().contiguous()
+        dpred = torch.empty_like(pred)
+        t0 = KernelTimer.begin('alpha_l1')
+        check(lib().saicv_alpha_l1_bwd(ptr(pred), ptr(alpha), ptr(trimap), ptr(g), b, p, ptr(dpred), stream()), 'alpha_l1_bwd')
+        KernelTimer.end(t0, 'alpha_l1', 0, (12 if trimap is None else 16) * b * p)
+        return dpred, None, None
+
+
+def _maps(name, pred, *others):
+    """pred [B, 1, H, W] or [B, H, W] and maps with the same number of pixels per sample -> fp32 contiguous [B, P] views"""
+    require_gpu(pred, *others)
+    b = pred.shape[0]
+    out = [_f32c(pred).view(b, -1)]
+    for t in others:
+        t2 = None if t is None else _f32c(t).view(b, -1)
+        if t2 is not None and t2.shape != out[0].shape:
+            raise ValueError(f'{name}: pred has {out[0].shape[1]} pixels per sample, another map {t2.shape[1]}')
+        out.append(t2)
+    return out
+
+
+def alpha_l1(pred, alpha, trimap=None):
+    """-> [B, 2] fp32: per sample (sum sqrt(((clamp(pred) - alpha) w)^2 + 1e-12), sum w); w = [trimap == 128], or 1 without a
+    trimap.  A pixel with w = 0 still adds sqrt(1e-12), as the reference's expression does."""
+    return AlphaL1Fn.apply(*_maps('alpha_l1', pred, alpha, trimap))
+
+
+class AlphaLossFn(torch.autograd.Function):
+    """The alpha loss itself as one autograd node: sum_b sums[b, 0] / (sum_b sums[b, 1] + 1) with a trimap (LocalAlphaLoss), or
+    / (B P) without (FusionAlphaLoss).  The same two kernels as AlphaL1Fn; the [B]-sized arithmetic around them is five small
+    launches forward and two backward instead of the two dozen that autograd records for the same expression in torch ops (alone
+    at batch 8, 1024^2 those made the fused LocalAlphaLoss launch-bound and slower than the composed one)."""
+
+    @staticmethod
+    def forward(ctx, pred, alpha, trimap):
+        b, p = pred.shape
+        L, dev = lib(), pred.device
+        sums = torch.empty((b, 2), dtype=torch.float32, device=dev)
+        partial = torch.empty(L.saicv_matting_ws_floats(b, p), dtype=torch.float32, device=dev)
+        t0 = KernelTimer.begin('alpha_l1')
+        check(L.saicv_alpha_l1_fwd(ptr(pred), ptr(alpha), ptr(trimap), b, p, ptr(partial), ptr(sums), stream()), 'alpha_l1_fwd')
+        KernelTimer.end(t0, 'alpha_l1', 0, (8 if trimap is None else 12) * b * p)
+        total = sums.sum(dim=0)
+        den = total[1] + 1. if trimap is not None else torch.full((), float(b * p), dtype=torch.float32, device=dev)
+        ctx.save_for_backward(pred, alpha, trimap, den)
+        return total[0] / den
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, alpha, trimap, den = ctx.saved_tensors
+        b, p = pred.shape
+        gs = (g.float() / den).reshape(1, 1).expand(b, 2).contiguous()
+        dpred = torch.empty_like(pred)
+        t0 = KernelTimer.begin('alpha_l1')
+        check(lib().saicv_alpha_l1_bwd(ptr(pred), ptr(alpha), ptr(trimap), ptr(gs), b, p, ptr(dpred), stream()), 'alpha_l1_bwd')
+        KernelTimer.end(t0, 'alpha_l1', 0, (12 if trimap is None else 16) * b * p)
+        return dpred, None, None
+
+
+def alpha_loss(pred, alpha, trimap=None):
+    """LocalAlphaLoss (trimap given: masked by [trimap == 128], denominator sum w + 1) / FusionAlphaLoss (no trimap: denominator
+    the number of pixels) of the reference as a scalar; see alpha_l1 for the sums"""
+    return AlphaLossFn.apply(*_maps('alpha_loss', pred, alpha, trimap))
+
+
+class CompositionL1Fn(torch.autograd.Function):
+    """pred [B, P]; fg, bg, image [B, 3 P] -> [B] = sum over pixels and channels of sqrt((ph fg + (1 - ph) bg - image)^2 + 1e-12):
+    CompositionLoss (SimpleAICV/human_matting/losses.py:265-287); the gradient goes to pred only"""
+
+    @staticmethod
+    def forward(ctx, pred, fg, bg, image):
+        b, p = pred.shape
+        L, dev = lib(), pred.device
+        sums = torch.empty((b,), dtype=torch.float32, device=dev)
+        partial = torch.empty(L.saicv_matting_ws_floats(b, p), dtype=torch.float32, device=dev)
+        t0 = KernelTimer.begin('composition_l1')
+        check(L.saicv_composition_l1_fwd(ptr(pred), ptr(fg), ptr(bg), ptr(image), b, p, ptr(partial), ptr(sums), stream()),
+              'composition_l1_fwd')
+        KernelTimer.end(t0, 'composition_l1', 0, 40 * b * p)
+        ctx.save_for_backward(pred, fg, bg, image)
+        return sums
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, fg, bg, image = ctx.saved_tensors
+        b, p = pred.shape
+        g = g.float().contiguous()
+        dpred = torch.empty_like(pred)
+        t0 = KernelTimer.begin('composition_l1')
+        check(lib().saicv_composition_l1_bwd(ptr(pred), ptr(fg), ptr(bg), ptr(image), ptr(g), b, p, ptr(dpred), stream()),
+              'composition_l1_bwd')
+        KernelTimer.end(t0, 'composition_l1', 0, 44 * b * p)
+        return dpred, None, None, None
+
+
+def composition_l1(pred, fg, bg, image):
+    """pred [B, 1, H, W]; fg, bg, image [B, 3, H, W] -> [B] fp32"""
+    require_gpu(pred, fg, bg, image)
+    b = pred.shape[0]
+    p2 = _f32c(pred).view(b, -1)
+    three = [_f32c(t).view(b, -1) for t in (fg, bg, image)]
+    if any(t.shape[1] != 3 * p2.shape[1] for t in three):
+        raise ValueError('composition_l1: fg, bg and image must hold three channels of the prediction\'s size')
+    return CompositionL1Fn.apply(p2, *three)
+
+
+class LaplacianL1Fn(torch.autograd.Function):
+    """pred, alpha [B, h, w], trimap or None -> sums [6, B]: sum |entry| of the six entries of ONE Laplacian pyramid of
+    d0 = (clamp(pred) - alpha) * w.  The reference (SimpleAICV/human_matting/losses.py:117-180, :206-262) builds two pyramids and
+    takes the l1 distance of their entries; the pyramid is linear, so that is the pyramid of the difference.  One launch per level
+    each way (csrc/matting.hip); the five coarser maps (a third of a map) are what the backward keeps."""
+
+    @staticmethod
+    def forward(ctx, pred, alpha, trimap, table):
+        b, h, w = pred.shape
+        L, dev = lib(), pred.device
+        tab = (ctypes.c_float * 25)(*table)
+        sums = torch.empty((LAP_LEVELS + 1, b), dtype=torch.float32, device=dev)
+        levels, cur = [], pred
+        t0 = KernelTimer.begin('lap_level')
+        for l in range(LAP_LEVELS):
+            hl, wl = h >> l, w >> l
+            nxt = torch.empty((b, hl // 2, wl // 2), dtype=torch.float32, device=dev)
+            partial = torch.empty(L.saicv_lap_level_ws_floats(b, hl, wl), dtype=torch.float32, device=dev)
+            top = l == LAP_LEVELS - 1
+            check(L.saicv_lap_level_fwd(ptr(cur), ptr(alpha) if l == 0 else 0, ptr(trimap) if l == 0 else 0, int(l == 0), b, hl, wl,
+                                        tab, ptr(nxt), ptr(partial), sums.data_ptr() + 4 * b * l,
+                                        sums.data_ptr() + 4 * b * LAP_LEVELS if top else 0, stream()), 'lap_level_fwd')
+            levels.append(nxt)
+            cur = nxt
+        KernelTimer.end(t0, 'lap_level', 50.0 * b * h * w * 4 / 3, (8 if trimap is None else 12) * b * h * w + 5 * b * h * w // 3 * 2)
+        ctx.save_for_backward(pred, alpha, trimap, *levels)
+        ctx.table = tuple(table)
+        return sums
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, alpha, trimap, *levels = ctx.saved_tensors
+        b, h, w = pred.shape
+        L, dev = lib(), pred.device
+        tab = (ctypes.c_float * 25)(*ctx.table)
+        g = g.float().contiguous()
+        maps = [pred] + list(levels)
+        gnext = None
+        t0 = KernelTimer.begin('lap_level')
+        for l in range(LAP_LEVELS - 1, -1, -1):
+            hl, wl = h >> l, w >> l
+            top = l == LAP_LEVELS - 1
+            gcur = torch.empty((b, hl, wl), dtype=torch.float32, device=dev)
+            check(L.saicv_lap_level_bwd(ptr(maps[l]), ptr(alpha) if l == 0 else 0, ptr(trimap) if l == 0 else 0, int(l == 0), b, hl, wl,
+                                        tab, ptr(gnext), ptr(maps[l + 1]) if top else 0, g.data_ptr() + 4 * b * l,
+                                        g.data_ptr() + 4 * b * LAP_LEVELS if top else 0, ptr(gcur), stream()), 'lap_level_bwd')
+            gnext = gcur
+        KernelTimer.end(t0, 'lap_level', 100.0 * b * h * w * 4 / 3, (12 if trimap is None else 16) * b * h * w + 5 * b * h * w // 3 * 3)
+        return gnext, None, None, None
+
+
+def laplacian_sums(pred, alpha, trimap=None, weights=None):
+    """-> sums [6, B] fp32 of the one-pyramid form; see laplacian_l1"""
+    pred2, alpha2, trimap2 = (None if t is None else _f32c(t) for t in (pred, alpha, trimap))
+    require_gpu(pred2, alpha2, trimap2)
+    if pred2.dim() == 4:
+        if pred2.shape[1] != 1:
+            raise ValueError(f'laplacian_l1: pred must be [B, 1, H, W] or [B, H, W], got {tuple(pred.shape)}')
+        pred2 = pred2.view(pred2.shape[0], pred2.shape[2], pred2.shape[3])
+    b, h, w = pred2.shape
+    if min(h, w) < LAP_MIN_SIDE:
+        raise ValueError(f'laplacian_l1: a {h} x {w} map has no five pyramid levels; both sides must be at least {LAP_MIN_SIDE}')
+    if tuple(alpha2.shape) != (b, h, w) or (trimap2 is not None and tuple(trimap2.shape) != (b, h, w)):
+        raise ValueError(f'laplacian_l1: alpha / trimap must be [{b}, {h}, {w}]')
+    table = laplacian_gauss_table() if weights is None else tuple(float(v) for v in torch.as_tensor(weights).reshape(-1).tolist())
+    if len(table) != 25:
+        raise ValueError('laplacian_l1: the weight table holds 25 values (5 x 5, row-major)')
+    return LaplacianL1Fn.apply(pred2, alpha2, trimap2, table)
+
+
+_lap_scales = {}
+
+
+def _lap_scale(device, b, h, w):
+    """1 / (elements of pyramid entry l) as a device tensor [6], made once per shape: the upload happens in the first (eager)
+    iteration, so a step captured afterwards holds no host-to-device copy"""
+    key = (device, b, h, w)
+    if key not in _lap_scales:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('laplacian_l1: the first call at a new shape uploads a 6-element table and cannot be captured; '
+                               'run one eager iteration first (config.step_graph_warmup >= 1)')
+        _lap_scales[key] = torch.tensor([1. / (b * (h >> l) * (w >> l)) for l in range(LAP_LEVELS + 1)], dtype=torch.float32,
+                                        device=device)
+    return _lap_scales[key]
+
+
+def laplacian_l1(pred, alpha, trimap=None, weights=None):
+    """LocalLaplacianLoss (trimap given: both maps are masked by [trimap == 128]) / FusionLaplacianLoss (no trimap) of the
+    reference: the sum over the six pyramid entries of their mean absolute difference.  pred [B, 1, H, W] probabilities (clamped
+    to [1e-4, 1 - 1e-4] inside), alpha [B, H, W]; weights: the 25 values of the 5x5 filter (default: laplacian_gauss_table()).
+    H, W >= 32 (ValueError otherwise, before any launch)."""
+    sums = laplacian_sums(pred, alpha, trimap, weights)
+    b, h, w = sums.shape[1], pred.shape[-2], pred.shape[-1]
+    return (sums.sum(dim=1) * _lap_scale(sums.device, b, h, w)).sum()
+
+
+class MattingFuseFn(torch.autograd.Function):
+    """collaborative_matting (SimpleAICV/human_matting/models/pfan_matting.py:434-454): fused = local [argmax == 1] + [argmax == 2]
+    over the first maximum of the three global probabilities; the gradient reaches local_pred where argmax == 1 and nothing else"""
+
+    @staticmethod
+    def forward(ctx, gp, local):
+        gp, (sb, sc, sp) = _tri_layout(gp)
+        b, p = gp.shape[0], gp.shape[2] * gp.shape[3]
+        fused = torch.empty_like(local)
+        t0 = KernelTimer.begin('matting_fuse')
+        check(lib().saicv_matting_fuse_fwd(ptr(gp), sb, sc, sp, ptr(local), b, p, ptr(fused), stream()), 'matting_fuse_fwd')
+        KernelTimer.end(t0, 'matting_fuse', 0, 20 * b * p)
+        ctx.save_for_backward(gp)
+        ctx.layout = (sb, sc, sp)
+        return fused
+
+    @staticmethod
+    def backward(ctx, dfused):
+        gp, = ctx.saved_tensors
+        b, p = gp.shape[0], gp.shape[2] * gp.shape[3]
+        sb, sc, sp = ctx.layout
+        dfused = dfused.float().contiguous()
+        dlocal = torch.empty_like(dfused)
+        t0 = KernelTimer.begin('matting_fuse')
+        check(lib().saicv_matting_fuse_bwd(ptr(gp), sb, sc, sp, ptr(dfused), b, p, ptr(dlocal), stream()), 'matting_fuse_bwd')
+        KernelTimer.end(t0, 'matting_fuse', 0, 20 * b * p)
+        return None, dlocal
+
+
+def collaborative_matting(global_pred, local_pred):
+    """global_pred [B, 3, H, W] (NCHW or channels-last memory), local_pred [B, 1, H, W] -> fused_pred [B, 1, H, W] fp32"""
+    require_gpu(global_pred, local_pred)
+    local = _f32c(local_pred)
+    if local.dim() != 4 or local.shape[1] != 1 or local.numel() * 3 != global_pred.numel():
+        raise ValueError(f'collaborative_matting: local_pred {tuple(local_pred.shape)} does not match global_pred {tuple(global_pred.shape)}')
+    return MattingFuseFn.apply(global_pred, local)
+
+
 # ------------------------------------------------------------------------------ Muon: grouped Newton-Schulz (csrc/muon.hip)
 MUON_TILE = 64
 MUON_TAB = 13           # int32 per problem, the layout of csrc/muon.hip

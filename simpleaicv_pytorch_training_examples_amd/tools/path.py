@@ -20,3 +20,5 @@ interactive_segmentation_dataset_path = os.path.join(_ROOT, 'interactive_segment
 ADE20Kdataset_path = os.path.join(_ROOT, 'ADE20K')
 # salient object detection
 salient_object_detection_dataset_path = os.path.join(_ROOT, 'salient_object_detection_dataset')
+# human matting
+human_matting_dataset_path = os.path.join(_ROOT, 'human_matting_dataset')
