@@ -555,6 +555,26 @@ int saicv_lap_level_bwd(const float* src, const float* alpha, const float* trima
                         const float* table, const float* gnext, const float* topcur, const float* gs, const float* gtop, float* gcur,
                         void* stream);
 
+/* ---- face and human parsing (human_parsing/losses.py:13-149 CELoss, MultiClassBCELoss, IoULoss, DiceLoss; face_parsing/losses.py
+ *      holds the same four) ----
+ * One pass over logits [rows][C] (bf16 or fp32, the NHWC view of the prediction, 16-byte aligned, 2 <= C <= 256) and labels fp32
+ * [rows] for everything the four losses read.  a = softmax(z) (sigmoid == 0) or sigmoid(z); q = clamp(a, 1e-4, 1 - 1e-4);
+ * I = q_t, S = sum_c q_c, U = max(S + 1 - I, 1e-4), D = S + 1 + 1e-4.  terms [3] fp32:
+ *   terms[0] = mean over rows of -log q_t (softmax) or mean over rows * C of -(y log q + (1 - y) log(1 - q)) (sigmoid),
+ *   terms[1] = mean over rows of 1 - I / U,   terms[2] = mean over rows of 1 - (2 I + 1e-4) / D.
+ * A label outside [0, C) adds nothing to any term, no gradient, and still counts in the denominators.  `partial`:
+ * saicv_pixel_class_terms_ws_floats(rows) floats; the means are ordered two-stage sums (no atomics).
+ * form: 0 = by class count (lane per row up to saicv_pixel_class_terms_lane_max_classes(), wavefront per row above),
+ * 1 = lane per row, 2 = wavefront per row (probes and tests). */
+size_t saicv_pixel_class_terms_ws_floats(size_t rows);
+int saicv_pixel_class_terms_lane_max_classes(void);
+int saicv_pixel_class_terms_fwd(int dtype, const void* logits, const float* label, size_t rows, int C, int sigmoid, int form,
+                                float* partial, float* terms, void* stream);
+/* dlogits (dtype and layout of logits) from gterms [3] = dL/dterms in device memory: the gradient passes through the clamp only
+ * where 1e-4 <= a_c <= 1 - 1e-4 (per element), then through the softmax or sigmoid */
+int saicv_pixel_class_terms_bwd(int dtype, const void* logits, const float* label, const float* gterms, size_t rows, int C,
+                                int sigmoid, int form, void* dlogits, void* stream);
+
 /* Streaming attention (any Nq / Nk, head dim 32 or 64, separate q / k / v with strides).
  * Replaces SAM Attention.forward + add_decomposed_rel_pos (reference interactive_segmentation/models/
  * segment_anything/image_encoder.py:116-184) and DETR's nn.MultiheadAttention calls with a float

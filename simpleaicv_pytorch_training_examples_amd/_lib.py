@@ -252,6 +252,10 @@ SIGNATURES = {
     'saicv_lap_level_ws_floats': (c_size_t, [c_int] * 3),
     'saicv_lap_level_fwd': (c_int, [_P, _P, _P] + [c_int] * 4 + [POINTER(ctypes.c_float)] + [_P] * 5),
     'saicv_lap_level_bwd': (c_int, [_P, _P, _P] + [c_int] * 4 + [POINTER(ctypes.c_float)] + [_P] * 6),
+    'saicv_pixel_class_terms_ws_floats': (c_size_t, [c_size_t]),
+    'saicv_pixel_class_terms_lane_max_classes': (c_int, []),
+    'saicv_pixel_class_terms_fwd': (c_int, [c_int, _P, _P, c_size_t, c_int, c_int, c_int, _P, _P, _P]),
+    'saicv_pixel_class_terms_bwd': (c_int, [c_int, _P, _P, _P, c_size_t, c_int, c_int, c_int, _P, _P]),
     'saicv_attention_stream_fwd': (c_int, [c_int, c_int, _PA, _P]),
     'saicv_attention_stream_bwd': (c_int, [c_int, c_int, _PA, _P]),
 }

@@ -631,6 +631,16 @@ int saicv_lap_level_bwd(const float* src, const float* alpha, const float* trima
     if (!table) { set_error("lap_level_bwd: null weight table"); return -1; }
     return lap_level_bwd(src, alpha, trimap, level0, B, h, w, table, gnext, topcur, gs, gtop, gcur, S(stream));
 }
+size_t saicv_pixel_class_terms_ws_floats(size_t rows) { return pixel_class_terms_ws_floats(rows); }
+int saicv_pixel_class_terms_lane_max_classes(void) { return pixel_class_terms_lane_max_classes(); }
+int saicv_pixel_class_terms_fwd(int dtype, const void* logits, const float* label, size_t rows, int C, int sigmoid, int form,
+                                float* partial, float* terms, void* stream) {
+    return pixel_class_terms_fwd(dtype, logits, label, rows, C, sigmoid, form, partial, terms, S(stream));
+}
+int saicv_pixel_class_terms_bwd(int dtype, const void* logits, const float* label, const float* gterms, size_t rows, int C,
+                                int sigmoid, int form, void* dlogits, void* stream) {
+    return pixel_class_terms_bwd(dtype, logits, label, gterms, rows, C, sigmoid, form, dlogits, S(stream));
+}
 int saicv_attention_stream_fwd(int dtype, int D, const saicv_attn_desc* desc, void* stream) {
     if (!desc) { set_error("attention_stream: null descriptor"); return -1; }
     return attention_stream(dtype, D, 0, desc, S(stream));

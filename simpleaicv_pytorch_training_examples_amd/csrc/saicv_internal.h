@@ -128,6 +128,13 @@ int lap_level_fwd(const float* src, const float* alpha, const float* trimap, int
                   float* next, float* partial, float* sum_e, float* sum_next, hipStream_t st);
 int lap_level_bwd(const float* src, const float* alpha, const float* trimap, int level0, int B, int h, int w, const float* table,
                   const float* gnext, const float* topcur, const float* gs, const float* gtop, float* gcur, hipStream_t st);
+// parsing.hip: form = 0 (by class count), 1 (lane per row, C <= 32), 2 (wavefront per row)
+size_t pixel_class_terms_ws_floats(size_t rows);
+int pixel_class_terms_lane_max_classes();
+int pixel_class_terms_fwd(int dtype, const void* logits, const float* label, size_t rows, int C, int sigmoid, int form,
+                          float* partial, float* terms, hipStream_t st);
+int pixel_class_terms_bwd(int dtype, const void* logits, const float* label, const float* gterms, size_t rows, int C, int sigmoid,
+                          int form, void* dlogits, hipStream_t st);
 // attn_stream.hip: which = 0 forward, 1 dQ pass, 2 dK/dV pass; desc = const saicv_attn_desc*
 int attention_stream(int dtype, int D, int which, const void* desc, hipStream_t st);
 

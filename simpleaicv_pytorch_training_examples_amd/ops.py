@@ -1699,6 +1699,91 @@ def pixel_softmax_ce(logits, label):
     return PixelSoftmaxCEFn.apply(logits, label)
 
 
+PIXEL_TERMS_FORMS = {'auto': 0, 'lane': 1, 'wave': 2}
+
+
+class PixelClassTermsFn(torch.autograd.Function):
+    """Everything the reference's parsing losses (SimpleAICV/human_parsing/losses.py:13-149: CELoss, MultiClassBCELoss, IoULoss,
+    DiceLoss) read of the prediction, as one kernel each way (csrc/parsing.hip): -> fp32 [3] = (CE or multi-class BCE, IoU loss,
+    Dice loss).  The logits stay in their dtype and NHWC layout; nothing per row is kept, the backward recomputes the row
+    statistics from its one read of the logits and takes dL/dterms from device memory (no host read)."""
+
+    @staticmethod
+    def forward(ctx, logits, label, sigmoid, form):
+        c = logits.shape[1]
+        rows = logits.numel() // c
+        L, dev = lib(), logits.device
+        partial = torch.empty(L.saicv_pixel_class_terms_ws_floats(rows), dtype=torch.float32, device=dev)
+        terms = torch.empty(3, dtype=torch.float32, device=dev)
+        t0 = KernelTimer.begin('pixel_class_terms')
+        check(L.saicv_pixel_class_terms_fwd(dtype_code(logits.dtype), ptr(logits), ptr(label), rows, c, sigmoid, form, ptr(partial),
+                                            ptr(terms), stream()), 'pixel_class_terms_fwd')
+        KernelTimer.end(t0, 'pixel_class_terms', 0, rows * c * logits.element_size())
+        ctx.save_for_backward(logits, label)
+        ctx.geom = (rows, c, sigmoid, form)
+        return terms
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, label = ctx.saved_tensors
+        rows, c, sigmoid, form = ctx.geom
+        g = g.float().contiguous()
+        dlog = torch.empty_like(logits)                      # preserves the NHWC strides of a 4-d prediction
+        t0 = KernelTimer.begin('pixel_class_terms')
+        check(lib().saicv_pixel_class_terms_bwd(dtype_code(logits.dtype), ptr(logits), ptr(label), ptr(g), rows, c, sigmoid, form,
+                                                ptr(dlog), stream()), 'pixel_class_terms_bwd')
+        KernelTimer.end(t0, 'pixel_class_terms', 0, 2 * rows * c * logits.element_size())
+        return dlog, None, None, None
+
+
+_pct_last = [None]        # (ref(logits), logits._version, ref(label), label._version, grad mode, logit type, form, terms)
+
+
+def _pct_forget(dead):
+    last = _pct_last[0]
+    if last is not None and (last[0] is dead or last[2] is dead):
+        _pct_last[0] = None
+
+
+def pixel_class_terms(logits, label, logit_type='softmax', form='auto'):
+    """logits: [B, C, H, W] (any strides; NHWC memory is used as it is) or the [rows, C] NHWC view, bf16 or fp32, 2 <= C <= 256;
+    label: float (or integer) class ids, [B, H, W] or [rows]; logit_type 'softmax' or 'sigmoid'.
+    -> fp32 [3]: with a = softmax / sigmoid of the logits, q = clamp(a, 1e-4, 1 - 1e-4), I = q_t, S = sum_c q_c:
+         [0] mean -log q_t (softmax: CELoss) or the mean binary cross-entropy over pixels and classes (sigmoid: MultiClassBCELoss),
+         [1] mean 1 - I / max(S + 1 - I, 1e-4) (IoULoss),  [2] mean 1 - (2 I + 1e-4) / (S + 1 + 1e-4) (DiceLoss).
+    A label outside [0, C) contributes to no term and no gradient and still counts in the means (the rule of pixel_softmax_ce).
+    A second call with the same `logits` object at the same `_version`, the same `label` and logit type returns the SAME tensor:
+    a criterion dict of several losses over one prediction costs one forward launch, and autograd adds the [3] gradients before
+    the one backward launch.  Only the last call is remembered, through weak references to `logits` and `label` (see
+    binary_seg_stats).  `form` picks the row mapping of csrc/parsing.hip ('lane', 'wave'; 'auto' = by class count)."""
+    require_gpu(logits, label)
+    if logit_type not in ('softmax', 'sigmoid'):
+        raise ValueError(f"pixel_class_terms: logit_type is 'softmax' or 'sigmoid', got {logit_type!r}")
+    last = _pct_last[0]
+    mode = (torch.is_grad_enabled(), logits.requires_grad)
+    if (last is not None and last[0]() is logits and last[1] == logits._version and last[2]() is label
+            and last[3] == label._version and last[4] == mode and last[5] == logit_type and last[6] == form):
+        return last[7]
+    x = logits
+    if x.dim() == 4:
+        x = _nhwc(x)
+        rows = x.shape[0] * x.shape[2] * x.shape[3]
+    elif x.dim() == 2:
+        x = x.contiguous()
+        rows = x.shape[0]
+    else:
+        raise ValueError('pixel_class_terms expects [B, C, H, W] logits or their [rows, C] NHWC view')
+    if x.data_ptr() % 16:
+        x = x.clone(memory_format=torch.preserve_format)
+    lab = label.reshape(-1).float().contiguous()
+    if lab.numel() != rows:
+        raise ValueError(f'pixel_class_terms: {rows} pixels but {lab.numel()} labels')
+    terms = PixelClassTermsFn.apply(x, lab, int(logit_type == 'sigmoid'), PIXEL_TERMS_FORMS[form])
+    _pct_last[0] = (weakref.ref(logits, _pct_forget), logits._version, weakref.ref(label, _pct_forget), label._version, mode,
+                    logit_type, form, terms)
+    return terms
+
+
 class CpfeConvsFn(torch.autograd.Function):
     """x [N*H*W, Cin], W_all [(1 + 9 nb) P, Cin] -> the concatenated CPFE block output [N, (1 + nb) P, H, W] in `dtype`, NHWC
     memory: LinearFn's GEMM with fp32 output (Z), then the tap gather of csrc/semseg.hip.  One node for both, so that the

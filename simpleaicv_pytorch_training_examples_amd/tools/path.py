@@ -22,3 +22,6 @@ ADE20Kdataset_path = os.path.join(_ROOT, 'ADE20K')
 salient_object_detection_dataset_path = os.path.join(_ROOT, 'salient_object_detection_dataset')
 # human matting
 human_matting_dataset_path = os.path.join(_ROOT, 'human_matting_dataset')
+# face parsing / human parsing
+face_parsing_dataset_path = os.path.join(_ROOT, 'face_parsing_dataset')
+human_parsing_dataset_path = os.path.join(_ROOT, 'human_parsing_dataset')
