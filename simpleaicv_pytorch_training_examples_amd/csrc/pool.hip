@@ -577,6 +577,7 @@ int maxpool_bwd(int dtype, const void* dout, const uint8_t* idx, void* dx, int N
                 int C, int OH, int OW, int K, int stride, int pad, hipStream_t st) {
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0, "maxpool_bwd: C=%d must be a multiple of %d", C, n);
+    SAICV_REQUIRE(K * K <= 255, "maxpool_bwd: window too large");
     const size_t total = (size_t)Nimg * H * W * (C / n);
     if (dtype == SAICV_DTYPE_BF16)
         hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(sgrid(total)), dim3(256), 0, st, (const bf16_t*)dout, idx, (bf16_t*)dx, Nimg, H, W, C, OH, OW, K, stride, pad);
