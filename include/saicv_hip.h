@@ -316,6 +316,41 @@ int saicv_bn_relu_maxpool_bwd(int dtype, const void* dout, const uint8_t* idx, c
                               const float* invstd, const float* scale, const float* shift, void* dy, float* dgamma, float* dbeta,
                               int accumulate, float* ws, int N, int H, int W, int C, int OH, int OW, int K, int stride, int pad,
                               void* stream);
+/* saicv_bn_relu_maxpool_fwd that also keeps, per pooled element and channel, the raw y at the recorded position: ya [N][OH][OW][C] in
+ * the data type.  out and idx are bit-identical to saicv_bn_relu_maxpool_fwd's. */
+int saicv_bn_relu_maxpool_fwd_keep(int dtype, const void* y, const float* scale, const float* shift, void* out, uint8_t* idx, void* ya,
+                                   int N, int H, int W, int C, int OH, int OW, int K, int stride, int pad, void* stream);
+/* The two per-channel sums of saicv_bn_relu_maxpool_bwd's first pass from dout and ya alone (both pooled size; neither y nor idx is
+ * read): sums[c] = sum g, sums[C + c] = sum g * (ya - mean) * invstd, g = dout * [scale * ya + shift > 0].  sums: 2 * C floats,
+ * zeroed here.  Same grid, accumulation order and reduction as that pass: bit-equal to its sums in deterministic mode. */
+int saicv_bn_relu_maxpool_bwd_sums(int dtype, const void* dout, const void* ya, const float* mean, const float* invstd,
+                                   const float* scale, const float* shift, float* sums, int N, int OH, int OW, int C, void* stream);
+/* The second pass of saicv_bn_relu_maxpool_bwd alone, from given sums (2 * C floats: saicv_bn_relu_maxpool_bwd_sums'): dy, and
+ * dgamma / dbeta written (accumulate = 0) or added to (1).  The same kernel: the same bits. */
+int saicv_bn_relu_maxpool_bwd_apply(int dtype, const void* dout, const uint8_t* idx, const void* y, const float* gamma, const float* mean,
+                                    const float* invstd, const float* scale, const float* shift, const float* sums, void* dy,
+                                    float* dgamma, float* dbeta, int accumulate, int N, int H, int W, int C, int OH, int OW, int K,
+                                    int stride, int pad, void* stream);
+/* The rest of the pooled stem's backward as ONE stream (csrc/stembwd.hip): dy = saicv_bn_relu_maxpool_bwd's second pass, formed per
+ * 32 pixels and multiplied straight into the weight gradient of the space-to-depth stem; dy is never stored.
+ *   H, W: the convolution output; y [N][H][W][CO]; dout, idx [N][(H + 1) / 2][(W + 1) / 2][CO]; x [N][H + R - 1][W + S - 1][CQ] (the image of
+ *   saicv_pack_input_s2d); sums: the 2 * CO floats of saicv_bn_relu_maxpool_bwd_sums (or of the first pass of saicv_bn_relu_maxpool_bwd);
+ *   dw fp32 [CO][R][S][CQ], ADDED into (what saicv_conv2d_wgrad gets); dgamma / dbeta written (accumulate = 0) or added to (1);
+ *   ws: saicv_stem_bwd_stream_ws_floats(N, H, W) floats (asked in the reduction mode of the launch).
+ * The weight gradient keeps saicv_conv2d_wgrad's association (its splits, 32-row steps, one chain per element, the ordered fold), so
+ * in deterministic mode dw is bit-equal to saicv_bn_relu_maxpool_bwd + saicv_conv2d_wgrad.
+ * saicv_stem_bwd_stream_ok: which parts of the route the block takes, non-zero only for bf16, CO = 64, CQ = 16, R = S = 4 (a 7 x 7
+ * stride-2 stem in space-to-depth form), pool (3, 2, 1), operands below 4 GiB and at least SAICV_STEM_BWD_MIN_ROWS rows (default
+ * 65536).  Bit 0: the forward keeps the maxima and the sums come from them; bit 1: the stream kernel replaces the second pass and
+ * saicv_conv2d_wgrad.  SAICV_STEM_BWD_STREAM: 0 nothing, 1 (default) bit 0 alone -- the stream kernel measures slower than the two
+ * kernels it replaces (profiles/stem_bwd_stream.md) and stays unrouted --, 2 both.  A pure function of its arguments and of the two
+ * switches, read per call. */
+int saicv_stem_bwd_stream_ok(int dtype, int N, int H, int W, int CO, int CQ, int R, int S, int pool_k, int pool_stride, int pool_pad);
+size_t saicv_stem_bwd_stream_ws_floats(int N, int H, int W);
+int saicv_stem_bwd_stream(int dtype, const void* dout, const uint8_t* idx, const void* y, const float* gamma, const float* mean,
+                          const float* invstd, const float* scale, const float* shift, const float* sums, const void* x, float* dw,
+                          float* dgamma, float* dbeta, int accumulate, float* ws, int N, int H, int W, int CO, int CQ, int R, int S,
+                          int pool_k, int pool_stride, int pool_pad, void* stream);
 /* nn.AdaptiveAvgPool2d((1,1)), resnet.py:203 */
 int saicv_avgpool_fwd(int dtype, const void* x, void* out, int N, int HW, int C, void* stream);
 int saicv_avgpool_bwd(int dtype, const void* dout, void* dx, int N, int HW, int C, void* stream);

@@ -136,6 +136,12 @@ SIGNATURES = {
     'saicv_maxpool_fwd': (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     'saicv_maxpool_bwd': (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     'saicv_bn_relu_maxpool_fwd': (c_int, [c_int, _P, _P, _P, _P, _P] + [c_int] * 9 + [_P]),
+    'saicv_bn_relu_maxpool_fwd_keep': (c_int, [c_int, _P, _P, _P, _P, _P, _P] + [c_int] * 9 + [_P]),
+    'saicv_bn_relu_maxpool_bwd_sums': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P] + [c_int] * 4 + [_P]),
+    'saicv_bn_relu_maxpool_bwd_apply': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int] + [c_int] * 9 + [_P]),
+    'saicv_stem_bwd_stream_ok': (c_int, [c_int] * 11),
+    'saicv_stem_bwd_stream_ws_floats': (c_size_t, [c_int, c_int, c_int]),
+    'saicv_stem_bwd_stream': (c_int, [c_int] + [_P] * 13 + [c_int, _P] + [c_int] * 10 + [_P]),
     'saicv_bn_relu_maxpool_bwd_ws_floats': (c_size_t, [c_int]),
     'saicv_bn_relu_maxpool_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P] + [c_int] * 9 + [_P]),
     'saicv_avgpool_fwd': (c_int, [c_int, _P, _P, c_int, c_int, c_int, _P]),

@@ -400,6 +400,36 @@ int saicv_bn_relu_maxpool_bwd(int dtype, const void* dout, const uint8_t* idx, c
     return bn_relu_maxpool_bwd(dtype, dout, idx, y, gamma, mean, invstd, scale, shift, dy, dgamma, dbeta, accumulate, ws, N, H, W, C,
                                OH, OW, K, stride, pad, S(stream));
 }
+int saicv_bn_relu_maxpool_fwd_keep(int dtype, const void* y, const float* scale, const float* shift, void* out, uint8_t* idx, void* ya,
+                                   int N, int H, int W, int C, int OH, int OW, int K, int stride, int pad, void* stream) {
+    return bn_relu_maxpool_fwd_keep(dtype, y, scale, shift, out, idx, ya, N, H, W, C, OH, OW, K, stride, pad, S(stream));
+}
+int saicv_bn_relu_maxpool_bwd_sums(int dtype, const void* dout, const void* ya, const float* mean, const float* invstd,
+                                   const float* scale, const float* shift, float* sums, int N, int OH, int OW, int C, void* stream) {
+    return bn_relu_maxpool_bwd_sums(dtype, dout, ya, mean, invstd, scale, shift, sums, N, OH, OW, C, S(stream));
+}
+int saicv_bn_relu_maxpool_bwd_apply(int dtype, const void* dout, const uint8_t* idx, const void* y, const float* gamma, const float* mean,
+                                    const float* invstd, const float* scale, const float* shift, const float* sums, void* dy,
+                                    float* dgamma, float* dbeta, int accumulate, int N, int H, int W, int C, int OH, int OW, int K,
+                                    int stride, int pad, void* stream) {
+    return bn_relu_maxpool_bwd_apply(dtype, dout, idx, y, gamma, mean, invstd, scale, shift, sums, dy, dgamma, dbeta, accumulate, N, H, W,
+                                     C, OH, OW, K, stride, pad, S(stream));
+}
+// BatchNorm-backward apply + weight gradient of the pooled space-to-depth stem as one stream (stembwd.hip)
+int saicv_stem_bwd_stream_ok(int dtype, int N, int H, int W, int CO, int CQ, int R, int S_, int pool_k, int pool_stride, int pool_pad) {
+    return stem_bwd_stream_ok(dtype, N, H, W, CO, CQ, R, S_, pool_k, pool_stride, pool_pad);
+}
+size_t saicv_stem_bwd_stream_ws_floats(int N, int H, int W) { return stem_bwd_stream_ws_floats(N, H, W); }
+int saicv_stem_bwd_stream(int dtype, const void* dout, const uint8_t* idx, const void* y, const float* gamma, const float* mean,
+                          const float* invstd, const float* scale, const float* shift, const float* sums, const void* x, float* dw,
+                          float* dgamma, float* dbeta, int accumulate, float* ws, int N, int H, int W, int CO, int CQ, int R, int S_,
+                          int pool_k, int pool_stride, int pool_pad, void* stream) {
+    SAICV_REQUIRE(stem_bwd_stream_supported(dtype, N, H, W, CO, CQ, R, S_, pool_k, pool_stride, pool_pad),
+                  "saicv_stem_bwd_stream: no form for dtype %d, N = %d, %d x %d outputs, Cout = %d, %d x %d taps over %d channels, pool (%d, %d, %d) "
+                  "(bf16, 64 channels, 4 x 4 taps over 16, pool (3, 2, 1), operands below 4 GiB)", dtype, N, H, W, CO, R, S_, CQ, pool_k,
+                  pool_stride, pool_pad);
+    return stem_bwd_stream(dout, idx, y, gamma, mean, invstd, scale, shift, sums, x, dw, dgamma, dbeta, accumulate, ws, N, H, W, S(stream));
+}
 
 int saicv_avgpool_fwd(int dtype, const void* x, void* out, int N, int HW, int C, void* stream) {
     return avgpool_fwd(dtype, x, out, N, HW, C, S(stream));

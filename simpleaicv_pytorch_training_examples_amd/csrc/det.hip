@@ -102,7 +102,10 @@ __global__ __launch_bounds__(256) void det_fold4_kernel(const float* __restrict_
 // elements, up to 512 parts) are one workgroup's worth of elements and `nparts` dependent L2 round trips per thread -- 20 ... 45 us
 // each, 1 ms of a deterministic ResNet-50 step.  Eight loader lanes per element quad bring 32 parts at a time into LDS (double
 // buffered), lane 0 adds them in ascending part order: bit for bit the chain's result (scripts/probes/det_fold_probe.py compares).
-constexpr int COOP_J = 8, COOP_E = 256 / COOP_J, COOP_CH = 32;
+// COOP_D chunks are in flight in REGISTERS ahead of the one being added: with the fetch of chunk c + 1 issued and awaited inside
+// iteration c, every chunk cost a whole L2 / HBM round trip (2 us) -- the stem's backward sums, 4096 parts of 128 elements, folded in
+// 250 us (profiles/stem_bwd_stream.md).  The chain and its order are untouched.
+constexpr int COOP_J = 8, COOP_E = 256 / COOP_J, COOP_CH = 32, COOP_D = 4, COOP_T = COOP_CH / COOP_J;
 __global__ __launch_bounds__(256) void det_fold4_coop_kernel(const float* __restrict__ part, size_t n, int nparts, size_t off, size_t count4,
                                                              float* __restrict__ dst) {
     __shared__ f32x4 buf[2][COOP_CH][COOP_E];
@@ -111,28 +114,42 @@ __global__ __launch_bounds__(256) void det_fold4_coop_kernel(const float* __rest
     const bool live = i < count4;
     const float* p = part + off + (live ? i : 0) * 4;
     const int chunks = (nparts + COOP_CH - 1) / COOP_CH;
-    auto load = [&](int c) {
-        f32x4 v[COOP_CH / COOP_J];
+    auto fetch = [&](f32x4 (&v)[COOP_T], int c) __attribute__((always_inline)) {
 #pragma unroll
-        for (int t = 0; t < COOP_CH / COOP_J; ++t) {
+        for (int t = 0; t < COOP_T; ++t) {
             const int k = c * COOP_CH + t * COOP_J + j;
             v[t] = (live && k < nparts) ? *reinterpret_cast<const f32x4*>(p + (size_t)k * n) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
-#pragma unroll
-        for (int t = 0; t < COOP_CH / COOP_J; ++t) buf[c & 1][t * COOP_J + j][e] = v[t];
     };
+    f32x4 v[COOP_D][COOP_T];
+#pragma unroll
+    for (int d = 0; d < COOP_D; ++d) fetch(v[d], d);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    load(0);
-    __syncthreads();
-    for (int c = 0; c < chunks; ++c) {
-        if (c + 1 < chunks) load(c + 1);                    // the other buffer: its last readers passed the barrier below
-        if (j == 0) {
-            const int cnt = min(COOP_CH, nparts - c * COOP_CH);
-            int kk = 0;
-            if (c == 0) { acc = buf[0][0][e]; kk = 1; }     // the chain starts FROM part 0 (not 0 + part 0: the sign of a zero)
-            for (; kk < cnt; ++kk) acc += buf[c & 1][kk][e];
+    for (int c0 = 0; c0 < chunks; c0 += COOP_D) {
+#pragma unroll
+        for (int d = 0; d < COOP_D; ++d) {                  // (a compile-time index: the chunks in flight are registers)
+            const int c = c0 + d;
+            if (c >= chunks) break;                         // uniform over the workgroup
+            // buffer c & 1: its last readers (chunk c - 2) passed the barrier of chunk c - 1
+#pragma unroll
+            for (int t = 0; t < COOP_T; ++t) buf[c & 1][t * COOP_J + j][e] = v[d][t];
+            fetch(v[d], c + COOP_D);
+            __syncthreads();
+            if (j == 0) {
+                const int cnt = min(COOP_CH, nparts - c * COOP_CH);
+                if (c > 0 && cnt == COOP_CH) {              // a whole chunk: its LDS reads issued back to back, then the same chain
+                    f32x4 t[COOP_CH];
+#pragma unroll
+                    for (int kk = 0; kk < COOP_CH; ++kk) t[kk] = buf[c & 1][kk][e];
+#pragma unroll
+                    for (int kk = 0; kk < COOP_CH; ++kk) acc += t[kk];
+                } else {
+                    int kk = 0;
+                    if (c == 0) { acc = buf[0][0][e]; kk = 1; }     // the chain starts FROM part 0 (not 0 + part 0: the sign of a zero)
+                    for (; kk < cnt; ++kk) acc += buf[c & 1][kk][e];
+                }
+            }
         }
-        __syncthreads();
     }
     if (j == 0 && live) {
         f32x4* d = reinterpret_cast<f32x4*>(dst + i * 4);

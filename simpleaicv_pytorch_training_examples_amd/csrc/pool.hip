@@ -5,6 +5,7 @@
 #include "common.h"
 #include "saicv_internal.h"
 #include "det.h"
+#include "poolbwd.h"
 
 namespace {
 
@@ -186,11 +187,13 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const T* __restrict__ 
 // KT > 0: the window size as a compile-time constant (the stem's 3): the window's loads are issued back to back.  With a run-time K the
 // kh / kw loops stay rolled and every load waits for the previous one -- nine L2 round trips per pooled element: 148 us forward and 211 us
 // in the reduction pass against ~95 us of HBM time each (r06 trace).
-template <typename T, int KT>
+// KEEP: the raw y at each recorded maximum goes to ya (pooled size) as well -- what the backward's per-channel sums need of y
+// (bn_relu_maxpool_bwd_reduce_kernel<T, -1>); out and idx are the same bits either way.
+template <typename T, int KT, bool KEEP = false>
 __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(const T* __restrict__ y, const float* __restrict__ scale,
                                                                   const float* __restrict__ shift, T* __restrict__ out,
-                                                                  uint8_t* __restrict__ idx, int Nimg, int H, int W, int C, int OH,
-                                                                  int OW, int K, int stride, int pad) {
+                                                                  uint8_t* __restrict__ idx, T* __restrict__ ya, int Nimg, int H, int W,
+                                                                  int C, int OH, int OW, int K, int stride, int pad) {
     constexpr int N = Chunk<T>::N;
     const int cpr = C / N;
     const size_t total = (size_t)Nimg * OH * OW * cpr;
@@ -204,10 +207,10 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(const T* __res
         const int ow = (int)(pix % OW); pix /= OW;
         const int oh = (int)(pix % OH);
         const int n = (int)(pix / OH);
-        float best[N];
+        float best[N], yb[N];
         int bi[N];
 #pragma unroll
-        for (int j = 0; j < N; ++j) { best[j] = -INFINITY; bi[j] = 0; }
+        for (int j = 0; j < N; ++j) { best[j] = -INFINITY; bi[j] = 0; yb[j] = 0.f; }
         bool first = true;
         if constexpr (KT > 0) {
             u32x4 raw[KT * KT];
@@ -230,7 +233,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(const T* __res
 #pragma unroll
                 for (int j = 0; j < N; ++j) {
                     const float z = round_through<T>(fmaxf(fmaf(sc[j], v[j], sh[j]), 0.f));
-                    if (first || z > best[j] || z != z) { best[j] = z; bi[j] = pos; }
+                    if (first || z > best[j] || z != z) { best[j] = z; bi[j] = pos; yb[j] = v[j]; }
                 }
                 first = false;
             }
@@ -246,7 +249,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(const T* __res
 #pragma unroll
                     for (int j = 0; j < N; ++j) {
                         const float z = round_through<T>(fmaxf(fmaf(sc[j], v[j], sh[j]), 0.f));
-                        if (first || z > best[j] || z != z) { best[j] = z; bi[j] = kh * K + kw; }
+                        if (first || z > best[j] || z != z) { best[j] = z; bi[j] = kh * K + kw; yb[j] = v[j]; }
                     }
                     first = false;
                 }
@@ -254,6 +257,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(const T* __res
         }
         const size_t o = (((size_t)(n * OH + oh)) * OW + ow) * C + cb * N;
         st_chunk(out + o, Chunk<T>::pack(best));
+        if constexpr (KEEP) st_chunk(ya + o, Chunk<T>::pack(yb));
         uint8_t packed[N];                                  // one 8- / 4-byte store instead of N byte stores (o is a multiple of N)
 #pragma unroll
         for (int j = 0; j < N; ++j) packed[j] = (uint8_t)bi[j];
@@ -342,8 +346,9 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_reduce_kernel(const T
         const size_t o = (((size_t)(n * OH + oh)) * OW + ow) * C + cb * N;
         float d[N];
         Chunk<T>::unpack(ld_chunk(dout + o), d);
-        uint8_t ib[N];
-        if (N == 8) {
+        uint8_t ib[N] = {};
+        if constexpr (KT < 0) {
+        } else if (N == 8) {
             const uint2 raw = *reinterpret_cast<const uint2*>(idx + o);
             __builtin_memcpy(ib, &raw, 8);
         } else {
@@ -353,7 +358,9 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_reduce_kernel(const T
         float ya[N];                                   // y at each channel's recorded maximum
 #pragma unroll
         for (int j = 0; j < N; ++j) ya[j] = 0.f;
-        if constexpr (KT > 0) {
+        if constexpr (KT < 0) {                        // the forward kept them (KEEP): `y` is that pooled-size tensor, no window gather
+            Chunk<T>::unpack(ld_chunk(y + o), ya);
+        } else if constexpr (KT > 0) {
             u32x4 raw[KT * KT];
 #pragma unroll
             for (int kh = 0; kh < KT; ++kh) {
@@ -524,27 +531,14 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_apply_k3s2_kernel(con
         for (int p = 0; p < 4; ++p) {
             if (!pok[p]) continue;
             const int r = p >> 1, c = p & 1;
-            float yv[N], g[N], o[N];
+            float yv[N];
             Chunk<T>::unpack(yr[p], yv);
+            bool use[4];
+            int want[4];
 #pragma unroll
-            for (int j = 0; j < N; ++j) g[j] = 0.f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int dyq = q >> 1, dxq = q & 1;
-                if ((r == 0 && dyq == 1) || (c == 0 && dxq == 1)) continue;        // an even row / column lies in window a (b) only
-                if (!wok[q]) continue;
-                const int kh = r == 0 ? 1 : (dyq == 0 ? 2 : 0), kw = c == 0 ? 1 : (dxq == 0 ? 2 : 0);
-                const int want = kh * 3 + kw;
-#pragma unroll
-                for (int j = 0; j < N; ++j) g[j] += (ib[q][j] == want) ? d[q][j] : 0.f;
-            }
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                const float gj = fmaf(sc[j], yv[j], sh[j]) > 0.f ? g[j] : 0.f;
-                o[j] = k0[j] * (gj - mg[j] - (yv[j] - mu[j]) * is[j] * mx[j]);
-            }
+            for (int q = 0; q < 4; ++q) use[q] = k3s2_window(r, c, q, wok[q], want[q]);
             const int h = 2 * a + r, w = 2 * b + c;
-            st_chunk(dy + ((size_t)(n * H + h) * W + w) * C + cb * N, Chunk<T>::pack(o));
+            st_chunk(dy + ((size_t)(n * H + h) * W + w) * C + cb * N, k3s2_dy<T>(yv, d, ib, use, want, sc, sh, k0, mg, mu, is, mx));
         }
     }
 }
@@ -586,20 +580,76 @@ int maxpool_bwd(int dtype, const void* dout, const uint8_t* idx, void* dx, int N
     return check_launch("maxpool_bwd");
 }
 
-int bn_relu_maxpool_fwd(int dtype, const void* y, const float* scale, const float* shift, void* out, uint8_t* idx, int Nimg, int H,
-                        int W, int C, int OH, int OW, int K, int stride, int pad, hipStream_t st) {
+// ya == nullptr: the plain forward; else the KEEP form (the raw y at each recorded maximum goes to ya as well)
+static int bn_relu_maxpool_fwd_launch(int dtype, const void* y, const float* scale, const float* shift, void* out, uint8_t* idx, void* ya,
+                                      int Nimg, int H, int W, int C, int OH, int OW, int K, int stride, int pad, hipStream_t st) {
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0 && 256 % (C / n) == 0, "bn_relu_maxpool_fwd: C=%d must be %d x a power of two <= 256", C, n);
     SAICV_REQUIRE(K * K <= 255, "bn_relu_maxpool_fwd: window too large");
     const size_t total = (size_t)Nimg * OH * OW * (C / n);
+#define POOL_FWD(TT, KT_, KEEP_) hipLaunchKernelGGL((bn_relu_maxpool_fwd_kernel<TT, KT_, KEEP_>), dim3(sgrid(total)), dim3(256), 0, st, (const TT*)y, scale, shift, (TT*)out, idx, (TT*)ya, Nimg, H, W, C, OH, OW, K, stride, pad)
     if (dtype == SAICV_DTYPE_BF16) {
-        if (K == 3) hipLaunchKernelGGL((bn_relu_maxpool_fwd_kernel<bf16_t, 3>), dim3(sgrid(total)), dim3(256), 0, st, (const bf16_t*)y, scale, shift, (bf16_t*)out, idx, Nimg, H, W, C, OH, OW, K, stride, pad);
-        else hipLaunchKernelGGL((bn_relu_maxpool_fwd_kernel<bf16_t, 0>), dim3(sgrid(total)), dim3(256), 0, st, (const bf16_t*)y, scale, shift, (bf16_t*)out, idx, Nimg, H, W, C, OH, OW, K, stride, pad);
+        if (ya) { if (K == 3) POOL_FWD(bf16_t, 3, true); else POOL_FWD(bf16_t, 0, true); }
+        else { if (K == 3) POOL_FWD(bf16_t, 3, false); else POOL_FWD(bf16_t, 0, false); }
     } else {
-        if (K == 3) hipLaunchKernelGGL((bn_relu_maxpool_fwd_kernel<float, 3>), dim3(sgrid(total)), dim3(256), 0, st, (const float*)y, scale, shift, (float*)out, idx, Nimg, H, W, C, OH, OW, K, stride, pad);
-        else hipLaunchKernelGGL((bn_relu_maxpool_fwd_kernel<float, 0>), dim3(sgrid(total)), dim3(256), 0, st, (const float*)y, scale, shift, (float*)out, idx, Nimg, H, W, C, OH, OW, K, stride, pad);
+        if (ya) { if (K == 3) POOL_FWD(float, 3, true); else POOL_FWD(float, 0, true); }
+        else { if (K == 3) POOL_FWD(float, 3, false); else POOL_FWD(float, 0, false); }
     }
+#undef POOL_FWD
     return check_launch("bn_relu_maxpool_fwd");
+}
+
+int bn_relu_maxpool_fwd(int dtype, const void* y, const float* scale, const float* shift, void* out, uint8_t* idx, int Nimg, int H,
+                        int W, int C, int OH, int OW, int K, int stride, int pad, hipStream_t st) {
+    return bn_relu_maxpool_fwd_launch(dtype, y, scale, shift, out, idx, nullptr, Nimg, H, W, C, OH, OW, K, stride, pad, st);
+}
+
+int bn_relu_maxpool_fwd_keep(int dtype, const void* y, const float* scale, const float* shift, void* out, uint8_t* idx, void* ya,
+                             int Nimg, int H, int W, int C, int OH, int OW, int K, int stride, int pad, hipStream_t st) {
+    SAICV_REQUIRE(ya != nullptr, "bn_relu_maxpool_fwd_keep: ya missing");
+    return bn_relu_maxpool_fwd_launch(dtype, y, scale, shift, out, idx, ya, Nimg, H, W, C, OH, OW, K, stride, pad, st);
+}
+
+// The two per-channel sums of bn_relu_maxpool_bwd's first pass from the maxima the forward kept: sums[0][c] = sum g, sums[1][c] =
+// sum g * xhat over the pooled elements, g = dout * [scale * ya + shift > 0].  Grid, thread -> element mapping, accumulation order,
+// LDS reduction and partial index are those of the pass over y, so the sums are its sums (bit for bit in deterministic mode).
+int bn_relu_maxpool_bwd_sums(int dtype, const void* dout, const void* ya, const float* mean, const float* invstd, const float* scale,
+                             const float* shift, float* sums, int Nimg, int OH, int OW, int C, hipStream_t st) {
+    const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
+    SAICV_REQUIRE(C % n == 0 && 256 % (C / n) == 0, "bn_relu_maxpool_bwd_sums: C=%d must be %d x a power of two <= 256", C, n);
+    SAICV_REQUIRE(Nimg > 0 && OH > 0 && OW > 0, "bn_relu_maxpool_bwd_sums: empty tensor");
+    if (hipMemsetAsync(sums, 0, 2 * (size_t)C * sizeof(float), st) != hipSuccess) { set_error("bn_relu_maxpool_bwd_sums: memset failed"); return -1; }
+    const size_t ptotal = (size_t)Nimg * OH * OW * (C / n);
+    DetParts det;
+    if (det.begin(st, sgrid(ptotal), (size_t)2 * C, "bn_relu_maxpool_bwd_sums")) return -1;
+    if (dtype == SAICV_DTYPE_BF16)
+        hipLaunchKernelGGL((bn_relu_maxpool_bwd_reduce_kernel<bf16_t, -1>), dim3(sgrid(ptotal)), dim3(256), 0, st, (const bf16_t*)dout, nullptr, (const bf16_t*)ya, mean, invstd, scale, shift, sums, Nimg, 0, 0, C, OH, OW, 0, 0, 0, det.sink());
+    else
+        hipLaunchKernelGGL((bn_relu_maxpool_bwd_reduce_kernel<float, -1>), dim3(sgrid(ptotal)), dim3(256), 0, st, (const float*)dout, nullptr, (const float*)ya, mean, invstd, scale, shift, sums, Nimg, 0, 0, C, OH, OW, 0, 0, 0, det.sink());
+    if (det.fold(sums, 0, (size_t)2 * C)) return -1;
+    return check_launch("bn_relu_maxpool_bwd_sums");
+}
+
+// The second pass alone, from given sums ([2][C]: of the first pass below, or of bn_relu_maxpool_bwd_sums): dy, dgamma, dbeta
+int bn_relu_maxpool_bwd_apply(int dtype, const void* dout, const uint8_t* idx, const void* y, const float* gamma, const float* mean,
+                              const float* invstd, const float* scale, const float* shift, const float* sums, void* dy, float* dgamma,
+                              float* dbeta, int accumulate, int Nimg, int H, int W, int C, int OH, int OW, int K, int stride, int pad,
+                              hipStream_t st) {
+    const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
+    SAICV_REQUIRE(C % n == 0 && 256 % (C / n) == 0, "bn_relu_maxpool_bwd: C=%d must be %d x a power of two <= 256", C, n);
+    SAICV_REQUIRE(K <= 2 * stride + 1, "bn_relu_maxpool_bwd: K=%d, stride=%d: more than 2 x 2 windows cover a pixel", K, stride);
+    const size_t total = (size_t)Nimg * H * W * (C / n);
+    // the stem's own geometry: one thread per 2 x 2 pixel block (any other window geometry: the per-pixel form)
+    const bool k3s2 = K == 3 && stride == 2 && pad == 1 && OH == (H + 1) / 2 && OW == (W + 1) / 2;
+    const size_t qtotal = (size_t)Nimg * ((H + 1) / 2) * ((W + 1) / 2) * (C / n);
+    if (dtype == SAICV_DTYPE_BF16) {
+        if (k3s2) hipLaunchKernelGGL(bn_relu_maxpool_bwd_apply_k3s2_kernel<bf16_t>, dim3(sgrid(qtotal)), dim3(256), 0, st, (const bf16_t*)dout, idx, (const bf16_t*)y, gamma, mean, invstd, scale, shift, sums, (bf16_t*)dy, dgamma, dbeta, accumulate, Nimg, H, W, C, OH, OW);
+        else hipLaunchKernelGGL(bn_relu_maxpool_bwd_apply_kernel<bf16_t>, dim3(sgrid(total)), dim3(256), 0, st, (const bf16_t*)dout, idx, (const bf16_t*)y, gamma, mean, invstd, scale, shift, sums, (bf16_t*)dy, dgamma, dbeta, accumulate, Nimg, H, W, C, OH, OW, K, stride, pad);
+    } else {
+        if (k3s2) hipLaunchKernelGGL(bn_relu_maxpool_bwd_apply_k3s2_kernel<float>, dim3(sgrid(qtotal)), dim3(256), 0, st, (const float*)dout, idx, (const float*)y, gamma, mean, invstd, scale, shift, sums, (float*)dy, dgamma, dbeta, accumulate, Nimg, H, W, C, OH, OW);
+        else hipLaunchKernelGGL(bn_relu_maxpool_bwd_apply_kernel<float>, dim3(sgrid(total)), dim3(256), 0, st, (const float*)dout, idx, (const float*)y, gamma, mean, invstd, scale, shift, sums, (float*)dy, dgamma, dbeta, accumulate, Nimg, H, W, C, OH, OW, K, stride, pad);
+    }
+    return check_launch("bn_relu_maxpool_bwd");
 }
 
 int bn_relu_maxpool_bwd(int dtype, const void* dout, const uint8_t* idx, const void* y, const float* gamma, const float* mean,
@@ -610,26 +660,19 @@ int bn_relu_maxpool_bwd(int dtype, const void* dout, const uint8_t* idx, const v
     SAICV_REQUIRE(C % n == 0 && 256 % (C / n) == 0, "bn_relu_maxpool_bwd: C=%d must be %d x a power of two <= 256", C, n);
     SAICV_REQUIRE(K <= 2 * stride + 1, "bn_relu_maxpool_bwd: K=%d, stride=%d: more than 2 x 2 windows cover a pixel", K, stride);
     if (hipMemsetAsync(ws, 0, 2 * (size_t)C * sizeof(float), st) != hipSuccess) { set_error("bn_relu_maxpool_bwd: memset failed"); return -1; }
-    const size_t total = (size_t)Nimg * H * W * (C / n), ptotal = (size_t)Nimg * OH * OW * (C / n);
-    // the stem's own geometry: one thread per 2 x 2 pixel block (any other window geometry: the per-pixel form)
-    const bool k3s2 = K == 3 && stride == 2 && pad == 1 && OH == (H + 1) / 2 && OW == (W + 1) / 2;
-    const size_t qtotal = (size_t)Nimg * ((H + 1) / 2) * ((W + 1) / 2) * (C / n);
+    const size_t ptotal = (size_t)Nimg * OH * OW * (C / n);
     DetParts det;
     if (det.begin(st, sgrid(ptotal), (size_t)2 * C, "bn_relu_maxpool_bwd")) return -1;
     if (dtype == SAICV_DTYPE_BF16) {
         if (K == 3) hipLaunchKernelGGL((bn_relu_maxpool_bwd_reduce_kernel<bf16_t, 3>), dim3(sgrid(ptotal)), dim3(256), 0, st, (const bf16_t*)dout, idx, (const bf16_t*)y, mean, invstd, scale, shift, ws, Nimg, H, W, C, OH, OW, K, stride, pad, det.sink());
         else hipLaunchKernelGGL((bn_relu_maxpool_bwd_reduce_kernel<bf16_t, 0>), dim3(sgrid(ptotal)), dim3(256), 0, st, (const bf16_t*)dout, idx, (const bf16_t*)y, mean, invstd, scale, shift, ws, Nimg, H, W, C, OH, OW, K, stride, pad, det.sink());
-        if (det.fold(ws, 0, (size_t)2 * C)) return -1;
-        if (k3s2) hipLaunchKernelGGL(bn_relu_maxpool_bwd_apply_k3s2_kernel<bf16_t>, dim3(sgrid(qtotal)), dim3(256), 0, st, (const bf16_t*)dout, idx, (const bf16_t*)y, gamma, mean, invstd, scale, shift, ws, (bf16_t*)dy, dgamma, dbeta, accumulate, Nimg, H, W, C, OH, OW);
-        else hipLaunchKernelGGL(bn_relu_maxpool_bwd_apply_kernel<bf16_t>, dim3(sgrid(total)), dim3(256), 0, st, (const bf16_t*)dout, idx, (const bf16_t*)y, gamma, mean, invstd, scale, shift, ws, (bf16_t*)dy, dgamma, dbeta, accumulate, Nimg, H, W, C, OH, OW, K, stride, pad);
     } else {
         if (K == 3) hipLaunchKernelGGL((bn_relu_maxpool_bwd_reduce_kernel<float, 3>), dim3(sgrid(ptotal)), dim3(256), 0, st, (const float*)dout, idx, (const float*)y, mean, invstd, scale, shift, ws, Nimg, H, W, C, OH, OW, K, stride, pad, det.sink());
         else hipLaunchKernelGGL((bn_relu_maxpool_bwd_reduce_kernel<float, 0>), dim3(sgrid(ptotal)), dim3(256), 0, st, (const float*)dout, idx, (const float*)y, mean, invstd, scale, shift, ws, Nimg, H, W, C, OH, OW, K, stride, pad, det.sink());
-        if (det.fold(ws, 0, (size_t)2 * C)) return -1;
-        if (k3s2) hipLaunchKernelGGL(bn_relu_maxpool_bwd_apply_k3s2_kernel<float>, dim3(sgrid(qtotal)), dim3(256), 0, st, (const float*)dout, idx, (const float*)y, gamma, mean, invstd, scale, shift, ws, (float*)dy, dgamma, dbeta, accumulate, Nimg, H, W, C, OH, OW);
-        else hipLaunchKernelGGL(bn_relu_maxpool_bwd_apply_kernel<float>, dim3(sgrid(total)), dim3(256), 0, st, (const float*)dout, idx, (const float*)y, gamma, mean, invstd, scale, shift, ws, (float*)dy, dgamma, dbeta, accumulate, Nimg, H, W, C, OH, OW, K, stride, pad);
     }
-    return check_launch("bn_relu_maxpool_bwd");
+    if (det.fold(ws, 0, (size_t)2 * C)) return -1;
+    return bn_relu_maxpool_bwd_apply(dtype, dout, idx, y, gamma, mean, invstd, scale, shift, ws, dy, dgamma, dbeta, accumulate, Nimg, H, W, C,
+                                     OH, OW, K, stride, pad, st);
 }
 
 int avgpool_fwd(int dtype, const void* x, void* out, int Nimg, int HW, int C, hipStream_t st) {

@@ -59,6 +59,26 @@ int c3_bwd_stream_rows(int M, int CO, int CI);
 int c3_bwd_stream(int M, int CO, int CI, const void* dz, const void* y, const void* mask, const float* coef, const void* x,
                   const void* wd, void* dx, float* dw, const EpiExtra* ex, int bs_rows, float* part_ws, hipStream_t st);
 size_t c3_bwd_stream_ws_floats(int M, int CO, int CI);
+// pool.hip: the pooled stem's forward that also keeps the raw y at each recorded maximum (ya, pooled size), and the two per-channel
+// sums of its backward taken from ya instead of from the windows of y
+int bn_relu_maxpool_fwd_keep(int dtype, const void* y, const float* scale, const float* shift, void* out, uint8_t* idx, void* ya,
+                             int Nimg, int H, int W, int C, int OH, int OW, int K, int stride, int pad, hipStream_t st);
+int bn_relu_maxpool_bwd_sums(int dtype, const void* dout, const void* ya, const float* mean, const float* invstd, const float* scale,
+                             const float* shift, float* sums, int Nimg, int OH, int OW, int C, hipStream_t st);
+// ... and the second pass of its backward alone, from given sums
+int bn_relu_maxpool_bwd_apply(int dtype, const void* dout, const uint8_t* idx, const void* y, const float* gamma, const float* mean,
+                              const float* invstd, const float* scale, const float* shift, const float* sums, void* dy, float* dgamma,
+                              float* dbeta, int accumulate, int Nimg, int H, int W, int C, int OH, int OW, int K, int stride, int pad,
+                              hipStream_t st);
+// stembwd.hip: BatchNorm-backward apply + weight gradient of the pooled space-to-depth stem as one stream (dy never stored).
+// H, W: the convolution output; _ok: which parts of the route the block takes (switches read per call): 0 none, bit 0 the sums
+// from the kept maxima, bit 1 the stream kernel
+bool stem_bwd_stream_supported(int dtype, int N, int H, int W, int CO, int cq, int taps_r, int taps_s, int pk, int ps, int pp);
+int stem_bwd_stream_ok(int dtype, int N, int H, int W, int CO, int cq, int taps_r, int taps_s, int pk, int ps, int pp);
+size_t stem_bwd_stream_ws_floats(int N, int H, int W);
+int stem_bwd_stream(const void* dout, const uint8_t* idx, const void* y, const float* gamma, const float* mean, const float* invstd,
+                    const float* scale, const float* shift, const float* sums, const void* x, float* dw, float* dgamma, float* dbeta,
+                    int accumulate, float* part_ws, int N, int H, int W, hipStream_t st);
 // bn.hip: the finalize step of BatchNorm backward alone: `rows` rows of partial sums -> dgamma, dbeta and the coefficients
 // ca, cb, cc of dy = ca * g + cb * y + cc at ws + 64 * C (ws: 67 * C floats)
 int bn_bwd_coeffs(const float* part_g, const float* part_gx, int rows, int C, size_t M, const float* gamma, const float* mean,

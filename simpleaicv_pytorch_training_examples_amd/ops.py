@@ -721,12 +721,26 @@ def _pooled_tail(ctx, cs, weight, gamma, beta, stride, pad, pool):
     poh, pow_ = (d.OH + 2 * pp - pk) // ps + 1, (d.OW + 2 * pp - pk) // ps + 1
     zp = _empty_nhwc(n, k, poh, pow_, y.dtype, y.device)
     idx = torch.empty((n, poh, pow_, k), dtype=torch.uint8, device=y.device)
-    t0 = KernelTimer.begin('bn_act_fwd')
-    check(lib().saicv_bn_relu_maxpool_fwd(dtype_code(y.dtype), ptr(y), ptr(cs.scale), ptr(cs.shift), ptr(zp), ptr(idx), n, d.OH, d.OW,
-                                          k, poh, pow_, pk, ps, pp, cs.st), 'bn_relu_maxpool_fwd')
     es = y.element_size()
-    KernelTimer.end(t0, 'bn_act_fwd', 0, float(cs.M) * k * es + float(n) * poh * pow_ * k * (es + 1))
+    # the routed backward (_stem_routed_backward) takes its per-channel sums from the raw y at the recorded maxima: the forward keeps
+    # them (pooled size).  The conditions only Python knows come first; no new entry point is fetched without them.  route: bit 0
+    # the sums from the kept maxima, bit 1 the stream kernel of csrc/stembwd.hip as well (saicv_stem_bwd_stream_ok)
+    ya, route = None, 0
+    if y.dtype == torch.bfloat16 and cs.s2d is not None and cs.training and ctx.needs_input_grad[1]:
+        route = lib().saicv_stem_bwd_stream_ok(dtype_code(y.dtype), n, d.OH, d.OW, k, d.C, d.R, d.S, pk, ps, pp)
+    if route > 0:
+        ya = _empty_nhwc(n, k, poh, pow_, y.dtype, y.device)
+        t0 = KernelTimer.begin('stem_pool_keep')
+        check(lib().saicv_bn_relu_maxpool_fwd_keep(dtype_code(y.dtype), ptr(y), ptr(cs.scale), ptr(cs.shift), ptr(zp), ptr(idx), ptr(ya),
+                                                   n, d.OH, d.OW, k, poh, pow_, pk, ps, pp, cs.st), 'bn_relu_maxpool_fwd_keep')
+        KernelTimer.end(t0, 'stem_pool_keep', 0, float(cs.M) * k * es + float(n) * poh * pow_ * k * (2 * es + 1))
+    else:
+        t0 = KernelTimer.begin('bn_act_fwd')
+        check(lib().saicv_bn_relu_maxpool_fwd(dtype_code(y.dtype), ptr(y), ptr(cs.scale), ptr(cs.shift), ptr(zp), ptr(idx), n, d.OH, d.OW,
+                                              k, poh, pow_, pk, ps, pp, cs.st), 'bn_relu_maxpool_fwd')
+        KernelTimer.end(t0, 'bn_act_fwd', 0, float(cs.M) * k * es + float(n) * poh * pow_ * k * (es + 1))
     _remember(ctx, cs, weight, gamma, beta, stride, pad, True, False, idx, (pk, ps, pp, poh, pow_, cs.scale, cs.shift))
+    ctx.stem_ya, ctx.stem_route = ya, route
     return zp
 
 
@@ -877,6 +891,52 @@ def _pooled_bn_backward(ctx, st, dz, gamma, y, idx, mean, invstd):
     return (dy, None, None, None) if direct_bn else (dy, None, dgamma, dbeta)
 
 
+def _stem_routed_backward(ctx, st, dz, x, weight, gamma, y, idx, mean, invstd):
+    """The pooled space-to-depth stem's backward when its forward kept the maxima (_pooled_tail, ctx.stem_route): the two per-channel
+    sums from pooled-size tensors (no pass over y), then either the second pass of the two-kernel backward and the weight gradient as
+    before (bit 0 alone), or BatchNorm-backward apply + weight gradient as one stream, csrc/stembwd.hip -- dy is never allocated
+    (bit 1).  unpack_wgrad_s2d is the last launch either way.  -> ConvBnActFn.backward's return tuple."""
+    pk, ps, pp, poh, pow_, scale, shift = ctx.pool
+    d = ctx.cfg[5]
+    L = lib()
+    dt, dev = y.dtype, y.device
+    n, k, oh, ow = y.shape
+    c = x.shape[1]
+    es = y.element_size()
+    pooled = float(n) * poh * pow_ * k
+    dgamma, dbeta, direct_bn = _bn_grad_buffers(gamma, ctx.beta_ref, k, dev)
+    sums = torch.empty(2 * k, dtype=torch.float32, device=dev)
+    t0 = KernelTimer.begin('stem_bwd_sums')
+    check(L.saicv_bn_relu_maxpool_bwd_sums(dtype_code(dt), ptr(dz), ptr(ctx.stem_ya), ptr(mean), ptr(invstd), ptr(scale), ptr(shift),
+                                           ptr(sums), n, poh, pow_, k, st), 'bn_relu_maxpool_bwd_sums')
+    KernelTimer.end(t0, 'stem_bwd_sums', 0, 2.0 * pooled * es)                  # dout + ya
+    flops = 2.0 * n * oh * ow * k * d.R * d.S * c
+    if ctx.stem_route & 2:
+        ws = torch.empty(L.saicv_stem_bwd_stream_ws_floats(n, oh, ow), dtype=torch.float32, device=dev)
+        dw = torch.zeros((k, d.R, d.S, c), dtype=torch.float32, device=dev)
+        t0 = KernelTimer.begin('stem_bwd_stream')
+        check(L.saicv_stem_bwd_stream(dtype_code(dt), ptr(dz), ptr(idx), ptr(y), ptr(gamma), ptr(mean), ptr(invstd), ptr(scale),
+                                      ptr(shift), ptr(sums), ptr(x), ptr(dw), ptr(dgamma), ptr(dbeta), int(direct_bn), ptr(ws), n, oh, ow,
+                                      k, c, d.R, d.S, pk, ps, pp, st), 'stem_bwd_stream')
+        # y, dout + idx, the space-to-depth image: each once
+        KernelTimer.end(t0, 'stem_bwd_stream', flops, float(n) * oh * ow * k * es + pooled * (es + 1) + float(x.numel()) * es)
+        dwt = _weight_grad_s2d(dw, weight, c, _arena_grad(weight))
+    else:
+        dy = _empty_nhwc(n, k, oh, ow, dt, dev)
+        t0 = KernelTimer.begin('stem_bwd_apply')
+        check(L.saicv_bn_relu_maxpool_bwd_apply(dtype_code(dt), ptr(dz), ptr(idx), ptr(y), ptr(gamma), ptr(mean), ptr(invstd), ptr(scale),
+                                                ptr(shift), ptr(sums), ptr(dy), ptr(dgamma), ptr(dbeta), int(direct_bn), n, oh, ow, k, poh,
+                                                pow_, pk, ps, pp, st), 'bn_relu_maxpool_bwd_apply')
+        KernelTimer.end(t0, 'stem_bwd_apply', 0, 2.0 * n * oh * ow * k * es + pooled * (es + 1))      # y + dy; dout + idx
+        t0 = KernelTimer.begin('igemm_tn')
+        dwt = _conv_weight_grad(d, dy, x, weight, st, ctx.s2d)
+        KernelTimer.end(t0, 'igemm_tn', flops, 0)
+    if direct_bn:
+        dgamma = dbeta = None
+    return (None, dwt, dgamma if ctx.needs_input_grad[2] else None, dbeta if ctx.needs_input_grad[3] else None, None,
+            None, None, None, None, None, None, None)
+
+
 def _c3_fused_backward(ctx, st, dz, dz_is_given, gate_in, dskip, x, weight, gamma, y, mask, mean, invstd):
     """The whole backward of a bottleneck block's third convolution (1 x 1, stride 1, behind BatchNorm + residual + ReLU) as one
     stream, csrc/c3bwd.hip: finalize launch (coefficients, dgamma, dbeta), then BatchNorm-backward apply + data gradient + weight
@@ -997,6 +1057,8 @@ class ConvBnActFn(torch.autograd.Function):
             fused = _c3_fused_backward(ctx, st, dz, dz is dz0, gate_in, dskip, x, weight, gamma, y, mask, mean, invstd)
             if fused is not None:
                 return fused
+        if ctx.pool is not None and ctx.stem_route > 0:
+            return _stem_routed_backward(ctx, st, dz, x, weight, gamma, y, mask, mean, invstd)
         if ctx.pool is not None:
             dy, dres, dgamma, dbeta = _pooled_bn_backward(ctx, st, dz, gamma, y, mask, mean, invstd)
         else:
