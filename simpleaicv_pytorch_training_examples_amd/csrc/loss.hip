@@ -4,6 +4,7 @@
 // Forward also emits the gradient w.r.t. the logits (scaled by 1/B; the caller multiplies by
 // the upstream scalar), so backward is a single scale pass.
 #include "common.h"
+#include "ordered_sum.h"
 #include "saicv_internal.h"
 
 namespace {
@@ -69,16 +70,11 @@ __global__ __launch_bounds__(256) void ce_soft_kernel(const float* __restrict__ 
     }
 }
 
-// mean over rows (single block, deterministic order)
+// mean over rows (single block, the fold of ordered_sum.h)
 __global__ __launch_bounds__(256) void mean_rows_kernel(const float* __restrict__ v, int B,
                                                         float* __restrict__ out) {
-    __shared__ float part[4];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < B; i += 256) s += v[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = (part[0] + part[1] + part[2] + part[3]) / (float)B;
+    const float total = fold_rows<1>(v, B, 1);
+    if (threadIdx.x == 0) out[0] = total / (float)B;
 }
 
 // out[i] = in[i] * scale[0]   (in fp32; out T)

@@ -13,29 +13,13 @@
 #include "common.h"
 #include "saicv_internal.h"
 #include "det.h"
+#include "maskterm.h"
+#include "ordered_sum.h"
 
 namespace {
 
-constexpr int ML_THREADS = 256;
+constexpr int ML_THREADS = 256;         // (four wavefronts: ordered_sum.h)
 constexpr int ML_CHUNKS = 8;            // 16-byte logit chunks per thread
-
-struct MaskTerm {
-    float p, bce, one_m_pt, af;
-};
-
-DEVINL MaskTerm mask_term(float x, float t, float alpha) {
-    MaskTerm r;
-    const float e = expf(-fabsf(x));
-    r.p = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-    r.bce = fmaxf(x, 0.f) - x * t + log1pf(e);
-    r.one_m_pt = 1.f - (r.p * t + (1.f - r.p) * (1.f - t));
-    r.af = alpha * t + (1.f - alpha) * (1.f - t);
-    return r;
-}
-
-DEVINL float pow_gamma(float v, float gamma) {
-    return gamma == 2.f ? v * v : powf(fmaxf(v, 0.f), gamma);
-}
 
 template <typename T>
 __global__ __launch_bounds__(ML_THREADS) void mask_loss_stats_kernel(const T* __restrict__ logits,
@@ -73,20 +57,13 @@ __global__ __launch_bounds__(ML_THREADS) void mask_loss_stats_kernel(const T* __
             }
         }
     }
-    __shared__ float red[ML_THREADS / 64][6];
+    // (this tail used to add the four wavefront sums to 0.f; block_tree starts from the first one.  The same bits: the two differ
+    // only when that first sum is -0, every acc[i] starts at +0.f and +0 + (-0) = +0, so no lane or wavefront sum is ever -0)
 #pragma unroll
     for (int i = 0; i < 6; ++i) acc[i] = wave_sum(acc[i]);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) red[wave][i] = acc[i];
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = 0.f;
-#pragma unroll
-        for (int w = 0; w < ML_THREADS / 64; ++w) v += red[w][threadIdx.x];
+    const float v = block_tree<6>(acc);
+    if (threadIdx.x < 6)
         saicv::det_add(det, &stats[(size_t)bm * 6 + threadIdx.x], (size_t)bm * 6 + threadIdx.x, blockIdx.x, v);      // pixel slab = partial
-    }
 }
 
 template <typename T>
@@ -116,6 +93,8 @@ __global__ __launch_bounds__(ML_THREADS) void mask_loss_grad_kernel(const T* __r
             }
 #pragma unroll
             for (int k = 0; k < N; ++k) {
+                // (mask_term_grad's operations in its order, written out: through the call the compiler schedules this unrolled
+                // loop differently and the bf16 kernel measured 9 % slower, 131.9 against 120.7 us at 8 x 4 x 1024 x 1024)
                 const MaskTerm m = mask_term(x[k], t[k], alpha);
                 const float sp = m.p * (1.f - m.p);
                 const float dpt = sp * (2.f * t[k] - 1.f);

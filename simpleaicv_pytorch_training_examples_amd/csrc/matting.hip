@@ -2,7 +2,7 @@
 // full-resolution fp32 maps, and collaborative_matting of SimpleAICV/human_matting/models/pfan_matting.py:434-454.
 //
 // Pixel kernels.  A workgroup owns 4096 consecutive pixels of one sample (256 lanes x 4 pixels x 4 rounds), reads every map once in
-// 16-byte chunks and leaves one partial row; a second launch adds the rows of a sample in index order.  No atomics: every sum is
+// 16-byte chunks and leaves one partial row; a second launch folds the rows of a sample (ordered_sum.h).  No atomics: every sum is
 // bit-reproducible in every mode.  ph = clamp(p, float32(1e-4), float32(1 - 1e-4)); every backward takes dL/dsums from device
 // memory and gives exactly 0 where p lies outside the clamp (bounds inclusive), as torch.clamp's backward does.
 //   trimap_stats     global_pred [B][3][P] through three strides (NCHW-contiguous and channels-last alike), trimap [B][P] ->
@@ -20,6 +20,7 @@
 // ring (the same operations in the same order as forward, so the sign is the forward's), P^T spreads a quarter of g_next to the
 // four pixels it averaged, and G^T is the adjoint of replicate padding -- a border pixel collects the taps that were clamped onto it.
 #include "common.h"
+#include "ordered_sum.h"
 #include "saicv_internal.h"
 
 namespace {
@@ -34,45 +35,12 @@ DEVINL float mt_sign(float e) { return (e > 0.f ? 1.f : 0.f) - (e < 0.f ? 1.f : 
 DEVINL f32x4 mt_ld4(const float* p) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p)); }
 DEVINL void mt_st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
-// the workgroup's sums -> dst[0 .. NS)
-template <int NS>
-DEVINL void mt_block_sums(float (&s)[NS], float* dst) {
-    __shared__ float wpart[4][NS];
-#pragma unroll
-    for (int j = 0; j < NS; ++j) s[j] = wave_sum(s[j]);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < NS; ++j) wpart[threadIdx.x >> 6][j] = s[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < NS) {
-        const int j = threadIdx.x;
-        dst[j] = ((wpart[0][j] + wpart[1][j]) + wpart[2][j]) + wpart[3][j];
-    }
-}
-
-// one workgroup per sample: out[b * sb + j * sj] = sum of partial[b][0 .. nblk)[j] for j < ns_out, lanes striding over the rows,
-// then a fixed tree
-__global__ __launch_bounds__(256) void mt_fold_kernel(const float* __restrict__ partial, int nblk, int ns, int ns_out,
-                                                      float* __restrict__ out, long sb, long sj) {
-    __shared__ float wpart[4][2];
-    const float* src = partial + (size_t)blockIdx.x * nblk * ns;
-    float s[2] = {0.f, 0.f};
-    for (int i = threadIdx.x; i < nblk; i += 256) {
-        s[0] += src[(size_t)i * ns];
-        if (ns > 1) s[1] += src[(size_t)i * ns + 1];
-    }
-    s[0] = wave_sum(s[0]);
-    s[1] = wave_sum(s[1]);
-    if ((threadIdx.x & 63) == 0) {
-        wpart[threadIdx.x >> 6][0] = s[0];
-        wpart[threadIdx.x >> 6][1] = s[1];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < ns_out) {
-        const int j = threadIdx.x;
-        out[(size_t)blockIdx.x * sb + j * sj] = ((wpart[0][j] + wpart[1][j]) + wpart[2][j]) + wpart[3][j];
-    }
+// one workgroup per sample: out[b * sb + j * sj] = sum of partial[b][0 .. nblk)[j] for j < NOUT of the NS columns of a partial row
+template <int NS, int NOUT>
+__global__ __launch_bounds__(256) void mt_fold_kernel(const float* __restrict__ partial, int nblk, float* __restrict__ out, long sb,
+                                                      long sj) {
+    const float total = fold_rows<NOUT>(partial + (size_t)blockIdx.x * nblk * NS, nblk, NS);
+    if (threadIdx.x < NOUT) out[(size_t)blockIdx.x * sb + (int)threadIdx.x * sj] = total;
 }
 
 // ------------------------------------------------------------------------------------------------ three-channel maps
@@ -185,7 +153,7 @@ __global__ __launch_bounds__(256) void trimap_stats_fwd_kernel(const float* __re
             tri_add(p, tm[i], t.smooth, s);
         }
     }
-    mt_block_sums<2>(s, partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2);
+    block_sums<2>(s, partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2);
 }
 
 __global__ __launch_bounds__(256) void trimap_stats_bwd_kernel(const float* __restrict__ gp, const float* __restrict__ trimap,
@@ -294,7 +262,7 @@ __global__ __launch_bounds__(256) void alpha_l1_fwd_kernel(const float* __restri
     } else {
         for (size_t i = e0 + threadIdx.x; i < e1; i += 256) alpha_add(pp[i], aa[i], mt_weight(tm, i), s);
     }
-    mt_block_sums<2>(s, partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2);
+    block_sums<2>(s, partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2);
 }
 
 __global__ __launch_bounds__(256) void alpha_l1_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ alpha,
@@ -379,7 +347,7 @@ __global__ __launch_bounds__(256) void composition_l1_kernel(const float* __rest
             if (BWD) out[off + i] = v;
         }
     }
-    if (!BWD) mt_block_sums<1>(s, out + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+    if (!BWD) block_sums<1>(s, out + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 int mt_check(const char* what, int B, size_t P) {
@@ -476,7 +444,7 @@ __global__ __launch_bounds__(256) void lap_fwd_kernel(const float* __restrict__ 
         next[((size_t)b * g.h2 + oy) * g.w2 + ox] = v;
         s[1] += fabsf(v);
     }
-    mt_block_sums<2>(s, partial + ((size_t)b * gridDim.x + tile) * 2);
+    block_sums<2>(s, partial + ((size_t)b * gridDim.x + tile) * 2);
 }
 
 // g_cur (level 0: dL/dpred) of the tile.  gnext: dL/dnext [B][h2][w2], or with topcur != null gtop[b] * sign(topcur) (the last
@@ -602,7 +570,7 @@ int trimap_stats_fwd(const float* gp, long sb, long sc, long sp, const float* tr
     if (!mt_al16(trimap)) t.mode = 0;
     const int nblk = mt_nblk(P);
     hipLaunchKernelGGL(trimap_stats_fwd_kernel, dim3(nblk, B), dim3(256), 0, st, gp, trimap, t, partial);
-    hipLaunchKernelGGL(mt_fold_kernel, dim3(B), dim3(256), 0, st, partial, nblk, 2, 2, stats, 2L, 1L);
+    hipLaunchKernelGGL((mt_fold_kernel<2, 2>), dim3(B), dim3(256), 0, st, partial, nblk, stats, 2L, 1L);
     return check_launch("trimap_stats_fwd");
 }
 
@@ -623,7 +591,7 @@ int alpha_l1_fwd(const float* pred, const float* alpha, const float* trimap, int
     const int vec = P % 4 == 0 && mt_al16(pred) && mt_al16(alpha) && mt_al16(trimap);
     const int nblk = mt_nblk(P);
     hipLaunchKernelGGL(alpha_l1_fwd_kernel, dim3(nblk, B), dim3(256), 0, st, pred, alpha, trimap, P, vec, partial);
-    hipLaunchKernelGGL(mt_fold_kernel, dim3(B), dim3(256), 0, st, partial, nblk, 2, 2, sums, 2L, 1L);
+    hipLaunchKernelGGL((mt_fold_kernel<2, 2>), dim3(B), dim3(256), 0, st, partial, nblk, sums, 2L, 1L);
     return check_launch("alpha_l1_fwd");
 }
 
@@ -644,7 +612,7 @@ int composition_l1_fwd(const float* pred, const float* fg, const float* bg, cons
     const int nblk = mt_nblk(P);
     hipLaunchKernelGGL(composition_l1_kernel<0>, dim3(nblk, B), dim3(256), 0, st, pred, fg, bg, image, (const float*)nullptr, P, vec,
                        partial);
-    hipLaunchKernelGGL(mt_fold_kernel, dim3(B), dim3(256), 0, st, partial, nblk, 1, 1, sums, 1L, 0L);
+    hipLaunchKernelGGL((mt_fold_kernel<1, 1>), dim3(B), dim3(256), 0, st, partial, nblk, sums, 1L, 0L);
     return check_launch("composition_l1_fwd");
 }
 
@@ -692,9 +660,9 @@ int lap_level_fwd(const float* src, const float* alpha, const float* trimap, int
     const int tiles = lap_tiles(g);
     hipLaunchKernelGGL(lap_fwd_kernel, dim3(tiles, B), dim3(256), 0, st, src, level0 ? alpha : nullptr, level0 ? trimap : nullptr, next,
                        partial, K, g);
-    hipLaunchKernelGGL(mt_fold_kernel, dim3(B), dim3(256), 0, st, partial, tiles, 2, 1, sum_e, 1L, 0L);
+    hipLaunchKernelGGL((mt_fold_kernel<2, 1>), dim3(B), dim3(256), 0, st, partial, tiles, sum_e, 1L, 0L);
     if (sum_next != nullptr)
-        hipLaunchKernelGGL(mt_fold_kernel, dim3(B), dim3(256), 0, st, partial + 1, tiles, 2, 1, sum_next, 1L, 0L);
+        hipLaunchKernelGGL((mt_fold_kernel<2, 1>), dim3(B), dim3(256), 0, st, partial + 1, tiles, sum_next, 1L, 0L);
     return check_launch("lap_level_fwd");
 }
 

@@ -24,8 +24,10 @@
 //   wave form (C <= 256): pixel_ce's mapping -- 32 rows per workgroup, one wavefront per row, lane l holding classes l + 64 j.
 // Both run the same row routine (pct_*<N, WAVE>): only the slot -> class map and the reductions differ.  The backward recomputes
 // the row statistics from the logits (nothing per row is kept: 4 bytes per row each way would be a tenth of the traffic at 20 bf16
-// classes); the gradient leaves through the same LDS span with 16-byte stores.  All means are ordered two-stage sums: no atomics.
+// classes); the gradient leaves through the same LDS span with 16-byte stores.  All means are ordered sums (ordered_sum.h): no atomics.
 #include "common.h"
+#include "ordered_sum.h"
+#include "rowspan.h"
 #include "saicv_internal.h"
 
 namespace {
@@ -37,28 +39,6 @@ constexpr int PCT_MAX_C = 256;
 constexpr float PCT_LO = 1e-4f, PCT_HI = 1.f - 1e-4f, PCT_EPS = 1e-4f;
 
 extern __shared__ __attribute__((aligned(16))) unsigned char pct_smem[];
-
-__host__ __device__ inline size_t pct_span_bytes(int tile_rows, int C, size_t elem) {
-    return ((size_t)tile_rows * C * elem + 15) & ~(size_t)15;
-}
-
-// global [e0, e0 + n) <-> LDS [0, n): 16-byte chunks, then the (last tile's) scalar tail
-template <typename T>
-DEVINL void pct_stage_in(const T* __restrict__ g, T* lds, size_t e0, int n) {
-    constexpr int EPC = ElemTraits<T>::EPC;
-    const int chunks = n / EPC;
-    for (int i = threadIdx.x; i < chunks; i += blockDim.x) st_chunk(lds + (size_t)i * EPC, ld_chunk_nt(g + e0 + (size_t)i * EPC));
-    for (int i = chunks * EPC + threadIdx.x; i < n; i += blockDim.x) lds[i] = g[e0 + i];
-}
-template <typename T>
-DEVINL void pct_stage_out(T* __restrict__ g, const T* lds, size_t e0, int n) {
-    constexpr int EPC = ElemTraits<T>::EPC;
-    const int chunks = n / EPC;
-    for (int i = threadIdx.x; i < chunks; i += blockDim.x) st_chunk(g + e0 + (size_t)i * EPC, ld_chunk(lds + (size_t)i * EPC));
-    for (int i = chunks * EPC + threadIdx.x; i < n; i += blockDim.x) g[e0 + i] = lds[i];
-}
-
-DEVINL int pct_label(float lab, int C) { return (lab >= 0.f && lab < (float)C) ? (int)lab : -1; }
 
 // slot j of a lane's registers holds class j (lane form, N = 32) or class lane + 64 j (wave form, N = 4)
 template <bool WAVE> DEVINL int pct_class(int j, int lane) { return WAVE ? lane + 64 * j : j; }
@@ -260,28 +240,21 @@ template <typename T, bool SIG>
 __global__ __launch_bounds__(256) void pct_lane_fwd_kernel(const T* __restrict__ logits, const float* __restrict__ label, int rows,
                                                            int C, float* __restrict__ partial) {
     T* lds = reinterpret_cast<T*>(pct_smem);
-    float* wpart = reinterpret_cast<float*>(pct_smem + pct_span_bytes(PCT_LANE_ROWS, C, sizeof(T)));
     const int r0 = blockIdx.x * PCT_LANE_ROWS;
     const int nrow = min(PCT_LANE_ROWS, rows - r0);
-    pct_stage_in(logits, lds, (size_t)r0 * C, nrow * C);
+    stage_in(logits, lds, (size_t)r0 * C, nrow * C);
     __syncthreads();
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x, lane = tid & 63;
     float out[3] = {0.f, 0.f, 0.f};
     if (tid < nrow) {
-        const int t = pct_label(label[r0 + tid], C);
+        const int t = class_label(label[r0 + tid], C);
         if (t >= 0) {
             float v[PCT_LANE_MAX_C];
             pct_load_row<PCT_LANE_MAX_C, false>(lds + (size_t)tid * C, C, lane, v);
             pct_row_fwd<PCT_LANE_MAX_C, false, SIG>(v, C, t, lane, out);
         }
     }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float s = wave_sum(out[k]);
-        if (lane == 0) wpart[wave * 3 + k] = s;
-    }
-    __syncthreads();
-    if (tid < 3) partial[(size_t)blockIdx.x * 3 + tid] = ((wpart[tid] + wpart[3 + tid]) + wpart[6 + tid]) + wpart[9 + tid];
+    block_sums<3>(out, partial + (size_t)blockIdx.x * 3);
 }
 
 template <typename T, bool SIG>
@@ -291,14 +264,14 @@ __global__ __launch_bounds__(256) void pct_lane_bwd_kernel(const T* __restrict__
     T* lds = reinterpret_cast<T*>(pct_smem);
     const int r0 = blockIdx.x * PCT_LANE_ROWS;
     const int nrow = min(PCT_LANE_ROWS, rows - r0);
-    pct_stage_in(logits, lds, (size_t)r0 * C, nrow * C);
+    stage_in(logits, lds, (size_t)r0 * C, nrow * C);
     __syncthreads();
     const int tid = threadIdx.x, lane = tid & 63;
     const float g[3] = {gterms[0], gterms[1], gterms[2]};
     if (tid < nrow) {
         // (a lane reads and writes only its own row of the span: no barrier between the two)
         T* row = lds + (size_t)tid * C;
-        const int t = pct_label(label[r0 + tid], C);
+        const int t = class_label(label[r0 + tid], C);
         float v[PCT_LANE_MAX_C];
         if (t >= 0) {
             pct_load_row<PCT_LANE_MAX_C, false>(row, C, lane, v);
@@ -310,7 +283,7 @@ __global__ __launch_bounds__(256) void pct_lane_bwd_kernel(const T* __restrict__
         pct_store_row<PCT_LANE_MAX_C, false>(row, C, lane, v);
     }
     __syncthreads();
-    pct_stage_out(dlogits, lds, (size_t)r0 * C, nrow * C);
+    stage_out(dlogits, lds, (size_t)r0 * C, nrow * C);
 }
 
 // -------------------------------------------------------------------------------------------------- wave form
@@ -318,17 +291,16 @@ template <typename T, bool SIG>
 __global__ __launch_bounds__(256) void pct_wave_fwd_kernel(const T* __restrict__ logits, const float* __restrict__ label, int rows,
                                                            int C, float* __restrict__ partial) {
     T* lds = reinterpret_cast<T*>(pct_smem);
-    float* wpart = reinterpret_cast<float*>(pct_smem + pct_span_bytes(PCT_WAVE_ROWS, C, sizeof(T)));
     const int r0 = blockIdx.x * PCT_WAVE_ROWS;
     const int nrow = min(PCT_WAVE_ROWS, rows - r0);
-    pct_stage_in(logits, lds, (size_t)r0 * C, nrow * C);
+    stage_in(logits, lds, (size_t)r0 * C, nrow * C);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float acc[3] = {0.f, 0.f, 0.f};
     for (int i = 0; i < PCT_WAVE_ROWS / 4; ++i) {
         const int lr = wave * (PCT_WAVE_ROWS / 4) + i;
         if (lr >= nrow) break;                                   // wave-uniform
-        const int t = pct_label(label[r0 + lr], C);
+        const int t = class_label(label[r0 + lr], C);
         if (t < 0) continue;                                     // wave-uniform
         float v[4], out[3];
         pct_load_row<4, true>(lds + (size_t)lr * C, C, lane, v);
@@ -336,13 +308,7 @@ __global__ __launch_bounds__(256) void pct_wave_fwd_kernel(const T* __restrict__
 #pragma unroll
         for (int k = 0; k < 3; ++k) acc[k] += out[k];
     }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) wpart[wave * 3 + k] = acc[k];
-    }
-    __syncthreads();
-    const int tid = threadIdx.x;
-    if (tid < 3) partial[(size_t)blockIdx.x * 3 + tid] = ((wpart[tid] + wpart[3 + tid]) + wpart[6 + tid]) + wpart[9 + tid];
+    block_fold<3>(acc, partial + (size_t)blockIdx.x * 3);           // wave-uniform already: block_fold, not block_sums
 }
 
 template <typename T, bool SIG>
@@ -352,7 +318,7 @@ __global__ __launch_bounds__(256) void pct_wave_bwd_kernel(const T* __restrict__
     T* lds = reinterpret_cast<T*>(pct_smem);
     const int r0 = blockIdx.x * PCT_WAVE_ROWS;
     const int nrow = min(PCT_WAVE_ROWS, rows - r0);
-    pct_stage_in(logits, lds, (size_t)r0 * C, nrow * C);
+    stage_in(logits, lds, (size_t)r0 * C, nrow * C);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const float g[3] = {gterms[0], gterms[1], gterms[2]};
@@ -361,7 +327,7 @@ __global__ __launch_bounds__(256) void pct_wave_bwd_kernel(const T* __restrict__
         const int lr = wave * (PCT_WAVE_ROWS / 4) + i;
         if (lr >= nrow) break;
         T* row = lds + (size_t)lr * C;
-        const int t = pct_label(label[r0 + lr], C);
+        const int t = class_label(label[r0 + lr], C);
         float v[4];
         if (t >= 0) {
             pct_load_row<4, true>(row, C, lane, v);
@@ -372,28 +338,14 @@ __global__ __launch_bounds__(256) void pct_wave_bwd_kernel(const T* __restrict__
         pct_store_row<4, true>(row, C, lane, v);                 // (a wavefront reads and writes only its own rows of the span)
     }
     __syncthreads();
-    pct_stage_out(dlogits, lds, (size_t)r0 * C, nrow * C);
+    stage_out(dlogits, lds, (size_t)r0 * C, nrow * C);
 }
 
 // terms[k] = (sum of the workgroup partials of term k, in a fixed order) / denominator
 __global__ __launch_bounds__(256) void pct_mean_kernel(const float* __restrict__ partial, int n, float inv0, float inv12,
                                                        float* __restrict__ terms) {
-    __shared__ float part[4][3];
-    float s[3] = {0.f, 0.f, 0.f};
-    for (int i = threadIdx.x; i < n; i += 256) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) s[k] += partial[(size_t)i * 3 + k];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        s[k] = wave_sum(s[k]);
-        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][k] = s[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int k = threadIdx.x;
-        terms[k] = (((part[0][k] + part[1][k]) + part[2][k]) + part[3][k]) * (k == 0 ? inv0 : inv12);
-    }
+    const float total = fold_rows<3>(partial, n, 3);
+    if (threadIdx.x < 3) terms[threadIdx.x] = total * (threadIdx.x == 0 ? inv0 : inv12);
 }
 
 int pct_check(const char* what, const void* logits, const float* label, size_t rows, int C, int form) {
@@ -414,7 +366,7 @@ template <typename T>
 void pct_launch_fwd(const T* logits, const float* label, int rows, int C, bool sig, bool lane, float* partial, hipStream_t st) {
     const int tile = lane ? PCT_LANE_ROWS : PCT_WAVE_ROWS;
     const int blocks = (rows + tile - 1) / tile;
-    const size_t smem = pct_span_bytes(tile, C, sizeof(T)) + 12 * sizeof(float);
+    const size_t smem = span_bytes(tile, C, sizeof(T));
     auto k = lane ? (sig ? pct_lane_fwd_kernel<T, true> : pct_lane_fwd_kernel<T, false>)
                   : (sig ? pct_wave_fwd_kernel<T, true> : pct_wave_fwd_kernel<T, false>);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(256), smem, st, logits, label, rows, C, partial);
@@ -425,7 +377,7 @@ void pct_launch_bwd(const T* logits, const float* label, const float* g, int row
                     hipStream_t st) {
     const int tile = lane ? PCT_LANE_ROWS : PCT_WAVE_ROWS;
     const int blocks = (rows + tile - 1) / tile;
-    const size_t smem = pct_span_bytes(tile, C, sizeof(T));
+    const size_t smem = span_bytes(tile, C, sizeof(T));
     auto k = lane ? (sig ? pct_lane_bwd_kernel<T, true> : pct_lane_bwd_kernel<T, false>)
                   : (sig ? pct_wave_bwd_kernel<T, true> : pct_wave_bwd_kernel<T, false>);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(256), smem, st, logits, label, g, rows, C, dlogits);

@@ -16,8 +16,9 @@
 //             a second launch adds the rows in index order.  No atomics: dw and db are bit-reproducible in every mode.
 //
 // Mask statistics.  prob, label fp32 [B][P] -> stats [B][4] = (sum bce, sum ph, sum l, sum ph * l) with ph = clamp(p, 1e-4f,
-// 1 - 1e-4f) and bce = -(l log ph + (1 - l) log(1 - ph)); one read of both arrays each way, ordered two-stage sums.
+// 1 - 1e-4f) and bce = -(l log ph + (1 - l) log(1 - ph)); one read of both arrays each way, the ordered sums of ordered_sum.h.
 #include "common.h"
+#include "ordered_sum.h"
 #include "saicv_internal.h"
 
 namespace {
@@ -161,7 +162,6 @@ __global__ __launch_bounds__(256, 4) void conv3x3_c1_bwd_kernel(const T* __restr
     __shared__ __attribute__((aligned(16))) float wl[C1_MAX_C * 9];
     __shared__ float dzt[C1_ZH * C1_ZW];
     __shared__ float red[C1_PASS * C1_RED_LD];
-    __shared__ float wsum[4];
     const int C = g.C, G = C / EPC;
     const int per = 256 / G, A = per * G;                               // active threads: whole pixels, a lane's chunk never changes
     int b = blockIdx.x;
@@ -238,10 +238,8 @@ __global__ __launch_bounds__(256, 4) void conv3x3_c1_bwd_kernel(const T* __restr
             ws[row + gg * NACC + ps * C1_PASS + v] = s;
         }
     }
-    accb = wave_sum(accb);
-    if ((tid & 63) == 0) wsum[tid >> 6] = accb;
-    __syncthreads();
-    if (tid == 0) ws[row + 9 * C] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    float sb[1] = {accb};
+    block_sums<1>(sb, ws + row + 9 * C);
 }
 
 // second stage: out[o] (+)= sum over the workgroup rows in index order; 16 columns x 16 row groups per workgroup
@@ -302,7 +300,6 @@ DEVINL void bss_add(float p, float l, float (&s)[4]) {
 // grid (blocks per sample, B): partial[b][blk][4]
 __global__ __launch_bounds__(256) void bss_fwd_kernel(const float* __restrict__ prob, const float* __restrict__ label, size_t P,
                                                       int vec, float* __restrict__ partial) {
-    __shared__ float wpart[4][4];
     const size_t off = (size_t)blockIdx.y * P, e0 = (size_t)blockIdx.x * BSS_SPAN;
     const size_t e1 = e0 + BSS_SPAN < P ? e0 + BSS_SPAN : P;
     const float* pp = prob + off;
@@ -318,39 +315,13 @@ __global__ __launch_bounds__(256) void bss_fwd_kernel(const float* __restrict__ 
     } else {
         for (size_t i = e0 + threadIdx.x; i < e1; i += 256) bss_add(pp[i], ll[i], s);
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s[j] = wave_sum(s[j]);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) wpart[threadIdx.x >> 6][j] = s[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const int j = threadIdx.x;
-        partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + j] = ((wpart[0][j] + wpart[1][j]) + wpart[2][j]) + wpart[3][j];
-    }
+    block_sums<4>(s, partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4);
 }
 
-// one workgroup per sample: stats[b][j] = sum of partial[b][0 .. nblk)[j], lanes striding over the blocks, then a fixed tree
+// one workgroup per sample: stats[b][j] = sum of partial[b][0 .. nblk)[j]
 __global__ __launch_bounds__(256) void bss_fold_kernel(const float* __restrict__ partial, int nblk, float* __restrict__ stats) {
-    __shared__ float wpart[4][4];
-    const float* src = partial + (size_t)blockIdx.x * nblk * 4;
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = threadIdx.x; i < nblk; i += 256) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s[j] += src[(size_t)i * 4 + j];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s[j] = wave_sum(s[j]);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) wpart[threadIdx.x >> 6][j] = s[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const int j = threadIdx.x;
-        stats[(size_t)blockIdx.x * 4 + j] = ((wpart[0][j] + wpart[1][j]) + wpart[2][j]) + wpart[3][j];
-    }
+    const float total = fold_rows<4>(partial + (size_t)blockIdx.x * nblk * 4, nblk, 4);
+    if (threadIdx.x < 4) stats[(size_t)blockIdx.x * 4 + threadIdx.x] = total;
 }
 
 DEVINL float bss_grad(float p, float l, float g0, float g1, float g3) {

@@ -19,10 +19,12 @@
 #include "common.h"
 #include "saicv_internal.h"
 #include "det.h"
+#include "maskterm.h"
+#include "ordered_sum.h"
 
 namespace {
 
-constexpr int ST_THREADS = 256;
+constexpr int ST_THREADS = 256;           // (four wavefronts: ordered_sum.h)
 
 struct Tap { int i0, i1; float l0, l1; };
 
@@ -35,28 +37,6 @@ DEVINL Tap tap4(int d, int n) {
     t.l1 = src - (float)t.i0;
     t.l0 = 1.f - t.l1;
     return t;
-}
-
-// ---- maskloss.hip's per-element terms (kept identical)
-struct MaskTerm { float p, bce, one_m_pt, af; };
-DEVINL MaskTerm mask_term(float x, float t, float alpha) {
-    MaskTerm r;
-    const float e = expf(-fabsf(x));
-    r.p = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-    r.bce = fmaxf(x, 0.f) - x * t + log1pf(e);
-    r.one_m_pt = 1.f - (r.p * t + (1.f - r.p) * (1.f - t));
-    r.af = alpha * t + (1.f - alpha) * (1.f - t);
-    return r;
-}
-DEVINL float pow_gamma(float v, float gamma) { return gamma == 2.f ? v * v : powf(fmaxf(v, 0.f), gamma); }
-DEVINL float loss_grad(float x, float t, float alpha, float gamma, float c0, float c1, float c2) {
-    const MaskTerm m = mask_term(x, t, alpha);
-    const float sp = m.p * (1.f - m.p);
-    const float dpt = sp * (2.f * t - 1.f);
-    const float w_g = pow_gamma(m.one_m_pt, gamma);
-    const float w_gm1 = gamma == 2.f ? m.one_m_pt : powf(fmaxf(m.one_m_pt, 0.f), gamma - 1.f);
-    const float dfocal = m.af * (gamma * w_gm1 * (-dpt) * m.bce + w_g * (m.p - t));
-    return c0 * dfocal + (c1 * t + c2) * sp;
 }
 
 // ------------------------------------------------------------------------------------------ hyper-network product
@@ -228,21 +208,13 @@ __global__ __launch_bounds__(ST_THREADS) void stats_up4_kernel(const T* __restri
             }
         }
     }
-    __shared__ float red[ST_THREADS / 64][6];
+    // (as in mask_loss_stats_kernel, this tail used to add the four wavefront sums to 0.f: the same bits as block_tree's
+    // ((w0 + w1) + w2) + w3, because every acc[i] starts at +0.f and +0 + (-0) = +0 -- no lane or wavefront sum is ever -0)
 #pragma unroll
     for (int i = 0; i < 6; ++i) acc[i] = wave_sum(acc[i]);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) red[wave][i] = acc[i];
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < ST_THREADS / 64; ++k) s += red[k][threadIdx.x];
-        // (column block, low-resolution row) = partial
+    const float s = block_tree<6>(acc);
+    if (threadIdx.x < 6)      // (column block, low-resolution row) = partial
         saicv::det_add(det, &stats[(size_t)bm * 6 + threadIdx.x], (size_t)bm * 6 + threadIdx.x, blockIdx.y * gridDim.x + blockIdx.x, s);
-    }
 }
 
 // d loss / d low[b, m, i, j]: the 8 x 8 output pixels around (4i, 4j) are re-interpolated from the low-resolution
@@ -282,7 +254,7 @@ __global__ __launch_bounds__(GU_T * GU_T) void grad_up4_tiled_kernel(const T* __
             const Tap th = tap4(d, h), tw = tap4(e, w);
             const int a0 = th.i0 - (i0 - 1), a1 = th.i1 - (i0 - 1), b0 = tw.i0 - (j0 - 1), b1 = tw.i1 - (j0 - 1);
             const float x = th.l0 * (tw.l0 * lowt[a0][b0] + tw.l1 * lowt[a0][b1]) + th.l1 * (tw.l0 * lowt[a1][b0] + tw.l1 * lowt[a1][b1]);
-            g = loss_grad(x, tg[(size_t)d * 4 * w + e], alpha, gamma, c0, c1, c2);
+            g = mask_term_grad(x, tg[(size_t)d * 4 * w + e], alpha, gamma, c0, c1, c2);
         }
         gt[dd][ee] = g;
     }

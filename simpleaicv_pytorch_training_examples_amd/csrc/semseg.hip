@@ -12,13 +12,15 @@
 //   outside it (torch.clamp's backward), decided by p_t < 1e-4 and q < 1e-4.  (The forward takes p_t and q from its one pass of
 //   exp(x - max) / sum, the backward from exp(x - lse): they can disagree only within rounding of a bound, where the loss is
 //   continuous -- the gradient's regime is the backward's decision alone.)
-// The mean is two ordered stages (a partial per workgroup, then one workgroup): no atomics, bit-reproducible in every mode.
+// The mean is the ordered two-stage sum of ordered_sum.h: no atomics, bit-reproducible in every mode.
 //
 // Gather.  Z [N*H*W][ldz] fp32 = x . W_all^T with W_all rows (1x1 weight | per dilated branch its nine taps, tap-major);
 //   out[n,h,w, 0:P] = Z[n,h,w, 0:P],  out[n,h,w, P(1+j)+k] = sum_t Z[n, h+(ty-1)d_j, w+(tx-1)d_j, P + 9P j + P t + k]
 // (fp32 sum in tap order, one rounding at the store; taps outside the image count as zero), and the transposed gather backward.
 // Every Z element is read by exactly one output element, every dZ element written by exactly one thread.
 #include "common.h"
+#include "ordered_sum.h"
+#include "rowspan.h"
 #include "saicv_internal.h"
 
 namespace {
@@ -28,24 +30,6 @@ constexpr int PCE_MAX_C = 256;        // four values per lane
 constexpr float PCE_LO = 1e-4f;
 
 extern __shared__ __attribute__((aligned(16))) unsigned char pce_smem[];
-
-__host__ __device__ inline size_t pce_span_bytes(int C, size_t elem) { return ((size_t)PCE_ROWS * C * elem + 15) & ~(size_t)15; }
-
-// global [e0, e0 + n) -> LDS [0, n): 16-byte chunks, then the (last tile's) scalar tail
-template <typename T>
-DEVINL void pce_stage_in(const T* __restrict__ g, T* lds, size_t e0, int n) {
-    constexpr int EPC = ElemTraits<T>::EPC;
-    const int chunks = n / EPC;
-    for (int i = threadIdx.x; i < chunks; i += blockDim.x) st_chunk(lds + (size_t)i * EPC, ld_chunk_nt(g + e0 + (size_t)i * EPC));
-    for (int i = chunks * EPC + threadIdx.x; i < n; i += blockDim.x) lds[i] = g[e0 + i];
-}
-template <typename T>
-DEVINL void pce_stage_out(T* __restrict__ g, const T* lds, size_t e0, int n) {
-    constexpr int EPC = ElemTraits<T>::EPC;
-    const int chunks = n / EPC;
-    for (int i = threadIdx.x; i < chunks; i += blockDim.x) st_chunk(g + e0 + (size_t)i * EPC, ld_chunk(lds + (size_t)i * EPC));
-    for (int i = chunks * EPC + threadIdx.x; i < n; i += blockDim.x) g[e0 + i] = lds[i];
-}
 
 // one row in registers: v[j] = x[lane + 64 j] (-inf beyond C)
 template <typename T>
@@ -68,16 +52,13 @@ DEVINL float pce_probs(const float (&v)[4], float lse, int t, int lane, float (&
     return wave_sum(s);
 }
 
-DEVINL int pce_label(float lab, int C) { return (lab >= 0.f && lab < (float)C) ? (int)lab : -1; }
-
 template <typename T>
 __global__ __launch_bounds__(256) void pixel_ce_fwd_kernel(const T* __restrict__ logits, const float* __restrict__ label, int rows,
                                                            int C, float* __restrict__ lse_out, float* __restrict__ partial) {
     T* lds = reinterpret_cast<T*>(pce_smem);
-    float* wpart = reinterpret_cast<float*>(pce_smem + pce_span_bytes(C, sizeof(T)));
     const int r0 = blockIdx.x * PCE_ROWS;
     const int nrow = min(PCE_ROWS, rows - r0);
-    pce_stage_in(logits, lds, (size_t)r0 * C, nrow * C);
+    stage_in(logits, lds, (size_t)r0 * C, nrow * C);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const float loss_lo = -logf(PCE_LO), loss_hi = -logf(1.f - PCE_LO);
@@ -88,7 +69,7 @@ __global__ __launch_bounds__(256) void pixel_ce_fwd_kernel(const T* __restrict__
         const T* row = lds + (size_t)lr * C;
         float v[4];
         pce_load_row(row, C, lane, v);
-        const int t = pce_label(label[r0 + lr], C);
+        const int t = class_label(label[r0 + lr], C);
         const float mx = wave_max(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
         // one exponential pass: the denominator and the mass of the classes other than t, reduced side by side
         float se = 0.f, so = 0.f;
@@ -110,21 +91,15 @@ __global__ __launch_bounds__(256) void pixel_ce_fwd_kernel(const T* __restrict__
         acc += loss;
         if (lane == 0) lse_out[r0 + lr] = lse;
     }
-    if (lane == 0) wpart[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = ((wpart[0] + wpart[1]) + wpart[2]) + wpart[3];
+    const float w[1] = {acc};                                        // wave-uniform already: block_fold, not block_sums
+    block_fold<1>(w, partial + blockIdx.x);
 }
 
 // loss = (sum of the workgroup partials, in a fixed order) / rows
 __global__ __launch_bounds__(256) void pixel_ce_mean_kernel(const float* __restrict__ partial, int n, int rows,
                                                             float* __restrict__ loss) {
-    __shared__ float part[4];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) loss[0] = (((part[0] + part[1]) + part[2]) + part[3]) / (float)rows;
+    const float total = fold_rows<1>(partial, n, 1);
+    if (threadIdx.x == 0) loss[0] = total / (float)rows;
 }
 
 template <typename T>
@@ -134,7 +109,7 @@ __global__ __launch_bounds__(256) void pixel_ce_bwd_kernel(const T* __restrict__
     T* lds = reinterpret_cast<T*>(pce_smem);
     const int r0 = blockIdx.x * PCE_ROWS;
     const int nrow = min(PCE_ROWS, rows - r0);
-    pce_stage_in(logits, lds, (size_t)r0 * C, nrow * C);
+    stage_in(logits, lds, (size_t)r0 * C, nrow * C);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const float inv_rows = 1.f / (float)rows, up = upstream[0];
@@ -145,7 +120,7 @@ __global__ __launch_bounds__(256) void pixel_ce_bwd_kernel(const T* __restrict__
         float v[4], p[4];
         pce_load_row(row, C, lane, v);
         const float lse = lse_in[r0 + lr];
-        const int t = pce_label(label[r0 + lr], C);
+        const int t = class_label(label[r0 + lr], C);
         const float q = pce_probs(v, lse, t, lane, p);
         bool live = false;
         if (t >= 0) {
@@ -163,7 +138,7 @@ __global__ __launch_bounds__(256) void pixel_ce_bwd_kernel(const T* __restrict__
         }
     }
     __syncthreads();
-    pce_stage_out(dlogits, lds, (size_t)r0 * C, nrow * C);
+    stage_out(dlogits, lds, (size_t)r0 * C, nrow * C);
 }
 
 // ------------------------------------------------------------------------------------------------ CPFE tap gather
@@ -275,11 +250,11 @@ int pixel_softmax_ce_fwd(int dtype, const void* logits, const float* label, size
     if (pce_check("pixel_softmax_ce_fwd", logits, rows, C)) return -1;
     const int blocks = (int)pixel_softmax_ce_ws_floats(rows);
     if (dtype == SAICV_DTYPE_BF16) {
-        const size_t smem = pce_span_bytes(C, sizeof(bf16_t)) + 16;
+        const size_t smem = span_bytes(PCE_ROWS, C, sizeof(bf16_t));
         hipLaunchKernelGGL(pixel_ce_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), smem, st, (const bf16_t*)logits, label, (int)rows, C,
                            lse, partial);
     } else {
-        const size_t smem = pce_span_bytes(C, sizeof(float)) + 16;
+        const size_t smem = span_bytes(PCE_ROWS, C, sizeof(float));
         hipLaunchKernelGGL(pixel_ce_fwd_kernel<float>, dim3(blocks), dim3(256), smem, st, (const float*)logits, label, (int)rows, C,
                            lse, partial);
     }
@@ -293,10 +268,10 @@ int pixel_softmax_ce_bwd(int dtype, const void* logits, const float* label, cons
     SAICV_REQUIRE(((uintptr_t)dlogits & 15) == 0 && dlogits != nullptr, "pixel_softmax_ce_bwd: the gradient must start on a 16-byte boundary");
     const int blocks = (int)pixel_softmax_ce_ws_floats(rows);
     if (dtype == SAICV_DTYPE_BF16)
-        hipLaunchKernelGGL(pixel_ce_bwd_kernel<bf16_t>, dim3(blocks), dim3(256), pce_span_bytes(C, sizeof(bf16_t)), st,
+        hipLaunchKernelGGL(pixel_ce_bwd_kernel<bf16_t>, dim3(blocks), dim3(256), span_bytes(PCE_ROWS, C, sizeof(bf16_t)), st,
                            (const bf16_t*)logits, label, lse, upstream, (int)rows, C, (bf16_t*)dlogits);
     else
-        hipLaunchKernelGGL(pixel_ce_bwd_kernel<float>, dim3(blocks), dim3(256), pce_span_bytes(C, sizeof(float)), st,
+        hipLaunchKernelGGL(pixel_ce_bwd_kernel<float>, dim3(blocks), dim3(256), span_bytes(PCE_ROWS, C, sizeof(float)), st,
                            (const float*)logits, label, lse, upstream, (int)rows, C, (float*)dlogits);
     return check_launch("pixel_softmax_ce_bwd");
 }

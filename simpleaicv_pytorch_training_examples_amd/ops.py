@@ -1705,6 +1705,53 @@ def softmax_cross_entropy(logits, label, soft=False):
     return SoftmaxCEFn.apply(logits, label, soft)
 
 
+class _LastCall:
+    """The last call of an entry whose result several losses over one prediction share: weak references to the two operands, their
+    versions, the grad mode and the entry's other arguments.  Only one call is remembered, and the entry dies with either operand,
+    so it never outlives the prediction it describes."""
+
+    def __init__(self):
+        self.entry = None
+
+    def _forget(self, dead):
+        e = self.entry
+        if e is not None and (e[0] is dead or e[1] is dead):
+            self.entry = None
+
+    @staticmethod
+    def _key(a, b, extras):
+        return (a._version, b._version, torch.is_grad_enabled(), a.requires_grad) + extras
+
+    def get(self, a, b, *extras):
+        e = self.entry
+        if e is not None and e[0]() is a and e[1]() is b and e[2] == self._key(a, b, extras):
+            return e[3]
+        return None
+
+    def put(self, a, b, result, *extras):
+        self.entry = (weakref.ref(a, self._forget), weakref.ref(b, self._forget), self._key(a, b, extras), result)
+        return result
+
+
+def _class_rows(logits, label, who):
+    """[B, C, H, W] logits (NHWC memory is used as it is) or their [rows, C] view, on a 16-byte boundary, and the labels as one fp32
+    row -> (x, lab, rows, c)"""
+    if logits.dim() == 4:
+        x = _nhwc(logits)
+        rows = x.shape[0] * x.shape[2] * x.shape[3]
+    elif logits.dim() == 2:
+        x = logits.contiguous()
+        rows = x.shape[0]
+    else:
+        raise ValueError(f'{who} expects [B, C, H, W] logits or their [rows, C] NHWC view')
+    if x.data_ptr() % 16:
+        x = x.clone(memory_format=torch.preserve_format)
+    lab = label.reshape(-1).float().contiguous()
+    if lab.numel() != rows:
+        raise ValueError(f'{who}: {rows} pixels but {lab.numel()} labels')
+    return x, lab, rows, x.shape[1]
+
+
 class PixelSoftmaxCEFn(torch.autograd.Function):
     """The reference's semantic-segmentation CELoss (SimpleAICV/semantic_segmentation/losses.py:13-43) as one kernel each way
     (csrc/semseg.hip): softmax over the class axis, clamp to [1e-4, 1 - 1e-4], -log at the labelled class, mean over the pixels.
@@ -1714,20 +1761,7 @@ class PixelSoftmaxCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, label):
         require_gpu(logits, label)
-        if logits.dim() == 4:
-            logits = _nhwc(logits)
-            n, c, h, w = logits.shape
-            rows = n * h * w
-        elif logits.dim() == 2:
-            logits = logits.contiguous()
-            rows, c = logits.shape
-        else:
-            raise ValueError('pixel_softmax_ce expects [B, C, H, W] logits or their [rows, C] NHWC view')
-        if logits.data_ptr() % 16:
-            logits = logits.clone(memory_format=torch.preserve_format)
-        label = label.reshape(-1).float().contiguous()
-        if label.numel() != rows:
-            raise ValueError(f'pixel_softmax_ce: {rows} pixels but {label.numel()} labels')
+        logits, label, rows, c = _class_rows(logits, label, 'pixel_softmax_ce')
         L, dev = lib(), logits.device
         lse = torch.empty(rows, dtype=torch.float32, device=dev)
         partial = torch.empty(L.saicv_pixel_softmax_ce_ws_floats(rows), dtype=torch.float32, device=dev)
@@ -1798,13 +1832,7 @@ class PixelClassTermsFn(torch.autograd.Function):
         return dlog, None, None, None
 
 
-_pct_last = [None]        # (ref(logits), logits._version, ref(label), label._version, grad mode, logit type, form, terms)
-
-
-def _pct_forget(dead):
-    last = _pct_last[0]
-    if last is not None and (last[0] is dead or last[2] is dead):
-        _pct_last[0] = None
+_pct_last = _LastCall()
 
 
 def pixel_class_terms(logits, label, logit_type='softmax', form='auto'):
@@ -1821,28 +1849,11 @@ def pixel_class_terms(logits, label, logit_type='softmax', form='auto'):
     require_gpu(logits, label)
     if logit_type not in ('softmax', 'sigmoid'):
         raise ValueError(f"pixel_class_terms: logit_type is 'softmax' or 'sigmoid', got {logit_type!r}")
-    last = _pct_last[0]
-    mode = (torch.is_grad_enabled(), logits.requires_grad)
-    if (last is not None and last[0]() is logits and last[1] == logits._version and last[2]() is label
-            and last[3] == label._version and last[4] == mode and last[5] == logit_type and last[6] == form):
-        return last[7]
-    x = logits
-    if x.dim() == 4:
-        x = _nhwc(x)
-        rows = x.shape[0] * x.shape[2] * x.shape[3]
-    elif x.dim() == 2:
-        x = x.contiguous()
-        rows = x.shape[0]
-    else:
-        raise ValueError('pixel_class_terms expects [B, C, H, W] logits or their [rows, C] NHWC view')
-    if x.data_ptr() % 16:
-        x = x.clone(memory_format=torch.preserve_format)
-    lab = label.reshape(-1).float().contiguous()
-    if lab.numel() != rows:
-        raise ValueError(f'pixel_class_terms: {rows} pixels but {lab.numel()} labels')
-    terms = PixelClassTermsFn.apply(x, lab, int(logit_type == 'sigmoid'), PIXEL_TERMS_FORMS[form])
-    _pct_last[0] = (weakref.ref(logits, _pct_forget), logits._version, weakref.ref(label, _pct_forget), label._version, mode,
-                    logit_type, form, terms)
+    terms = _pct_last.get(logits, label, logit_type, form)
+    if terms is None:
+        x, lab, _, _ = _class_rows(logits, label, 'pixel_class_terms')
+        terms = _pct_last.put(logits, label, PixelClassTermsFn.apply(x, lab, int(logit_type == 'sigmoid'), PIXEL_TERMS_FORMS[form]),
+                              logit_type, form)
     return terms
 
 
@@ -2007,13 +2018,7 @@ class BinarySegStatsFn(torch.autograd.Function):
         return dprob, None
 
 
-_bss_last = [None]        # (ref(prob), prob._version, ref(label), label._version, grad mode, stats): the last call only
-
-
-def _bss_forget(dead):
-    last = _bss_last[0]
-    if last is not None and (last[0] is dead or last[2] is dead):
-        _bss_last[0] = None
+_bss_last = _LastCall()
 
 
 def binary_seg_stats(prob, label):
@@ -2027,11 +2032,9 @@ def binary_seg_stats(prob, label):
     require_gpu(prob, label)
     if prob.dtype != torch.float32 or not prob.is_contiguous():
         raise ValueError('binary_seg_stats: prob must be fp32 and contiguous')
-    last = _bss_last[0]
-    mode = (torch.is_grad_enabled(), prob.requires_grad)
-    if (last is not None and last[0]() is prob and last[1] == prob._version and last[2]() is label
-            and last[3] == label._version and last[4] == mode):
-        return last[5]
+    stats = _bss_last.get(prob, label)
+    if stats is not None:
+        return stats
     b = prob.shape[0]
     p2 = prob.view(b, -1)
     l2 = label.reshape(b, -1)
@@ -2039,9 +2042,7 @@ def binary_seg_stats(prob, label):
         l2 = l2.float().contiguous()
     if l2.shape != p2.shape:
         raise ValueError(f'binary_seg_stats: prob has {p2.shape[1]} elements per sample, label {l2.shape[1]}')
-    stats = BinarySegStatsFn.apply(p2, l2)
-    _bss_last[0] = (weakref.ref(prob, _bss_forget), prob._version, weakref.ref(label, _bss_forget), label._version, mode, stats)
-    return stats
+    return _bss_last.put(prob, label, BinarySegStatsFn.apply(p2, l2))
 
 
 # ------------------------------------------------------------------------------ human matting (csrc/matting.hip)

@@ -43,6 +43,66 @@ def stats_judge(p, label, g=None):
     return out
 
 
+# (B, P) of the summation-order test: both lane forms (P % 4 == 0 or not), one and two workgroups per sample, and 257 and 258 workgroup
+# partials per sample -- the smallest counts at which the fold's second stride trip has one lane and two lanes at work
+ORDER_CASES = [(2, 1), (2, 4099), (2, 4100), (2, 1048583), (1, 1052680)]
+ORDER_SPAN = 4096                            # elements of one sample per workgroup (BSS_SPAN of csrc/salient.hip)
+
+
+def order_inputs(B, P):
+    """p, label = torch.rand [B, P] fp32, drawn one after the other from one generator seeded with P"""
+    g = torch.Generator().manual_seed(P)
+    return torch.rand(B, P, generator=g), torch.rand(B, P, generator=g)
+
+
+def _lanes_then_tree(rounds):
+    """rounds float32 [n, R, 256]: lane t of workgroup n adds rounds[n, 0, t], rounds[n, 1, t], ... to +0 in that order; then the
+    wave_sum butterfly of csrc/common.h inside each 64-lane wavefront (partners lane ^ 1, ^ 2, the mirror within 8 lanes = ^ 7, the
+    mirror within 16 = ^ 15, ^ 16, ^ 32: fp32 addition commutes, so every lane ends with the same bits), then ((w0 + w1) + w2) + w3.
+    -> float32 [n]"""
+    assert rounds.dtype == np.float32
+    v = np.zeros((rounds.shape[0], 256), dtype=np.float32)
+    for r in range(rounds.shape[1]):
+        v = v + rounds[:, r]
+    lane = np.arange(256)
+    for mask in (1, 2, 7, 15, 16, 32):
+        v = v + v[:, lane ^ mask]
+    w = v[:, ::64]
+    out = ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+    assert out.dtype == np.float32
+    return out
+
+
+def ordered_sum(x, vec):
+    """The fp32 sum of x (float32 [P], no element -0) in the order of csrc/ordered_sum.h as binary_seg_stats runs it: a workgroup per
+    ORDER_SPAN elements -- vec: lane t takes elements 4 t .. 4 t + 3 of each round of 1024, in order; scalar: lane t takes element
+    t of each round of 256 -- then the fold of the workgroup partials with lane stride 256.  An element past the end is +0 here and
+    skipped on the GPU: s + 0 == s in bits for every s but -0, and a sum that starts at +0 never becomes -0."""
+    x = np.asarray(x, dtype=np.float32)
+    nblk = -(-x.size // ORDER_SPAN)
+    xp = np.zeros(nblk * ORDER_SPAN, dtype=np.float32)
+    xp[:x.size] = x
+    if vec:
+        rounds = xp.reshape(nblk, 4, 256, 4).transpose(0, 1, 3, 2).reshape(nblk, 16, 256)      # [n, round * 4 + j, lane]
+    else:
+        rounds = xp.reshape(nblk, 16, 256)
+    part = _lanes_then_tree(rounds)
+    trips = -(-nblk // 256)
+    pp = np.zeros(trips * 256, dtype=np.float32)
+    pp[:nblk] = part
+    return _lanes_then_tree(pp.reshape(1, trips, 256))[0]
+
+
+def ordered_stats_emulation(p, label):
+    """columns 1 (sum clamp(p)) and 2 (sum label) of binary_seg_stats in its own summation order -> float32 [B, 2].  Both are pure fp32
+    additions (the clamp selects, it does not round): the GPU's bits can be predicted exactly."""
+    B, P = p.shape
+    ph = torch.clamp(p, min=LO, max=HI).numpy()
+    assert ph.dtype == np.float32
+    vec = P % 4 == 0                         # (the tests' operands are fresh allocations: 16-byte aligned)
+    return np.array([[ordered_sum(ph[b], vec), ordered_sum(label[b].numpy(), vec)] for b in range(B)], dtype=np.float32)
+
+
 def loss_from_stats(stats, P, name, smooth=SMOOTH):
     """the reference formulas of BCELoss / BCEIouloss / BCEDiceLoss on the four sums (any float dtype)"""
     bce, sp, sl, inter = stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3]

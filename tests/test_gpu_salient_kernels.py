@@ -180,6 +180,23 @@ def test_stats_exact_operands_are_bit_exact(case, det):
     assert torch.equal(stats, again) and torch.equal(dp, dp2)
 
 
+@pytest.mark.parametrize('det', [False, True])
+@pytest.mark.parametrize('case', S.ORDER_CASES)
+def test_stats_sums_follow_the_stated_order_bit_for_bit(case, det):
+    """sum clamp(p) and sum label are pure fp32 additions: the kernel's bits equal the NumPy emulation of the ordered sum
+    (S.ordered_stats_emulation; tests/test_salient_host.py shows that a sequential sum gives other bits at these sizes)"""
+    ops, _ = _ops()
+    B, P = case
+    p, label = S.order_inputs(B, P)
+    want = torch.from_numpy(S.ordered_stats_emulation(p, label))
+    prev = ops.set_deterministic(det)
+    try:
+        stats, _ = _stats_call(p, label, _upstream(B))
+    finally:
+        ops.set_deterministic(prev)
+    assert torch.equal(stats[:, 1:3], want), (stats[:, 1:3], want)
+
+
 @pytest.mark.parametrize('case', STATS_CASES)
 def test_stats_regimes_and_gradient_bounds(case):
     B, P = case

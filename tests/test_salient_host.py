@@ -50,6 +50,28 @@ def test_stats_judge_gradient_equals_autograd_of_the_reference_formulas():
     assert bool((j['dp_mag'] >= j['dp'].abs() * (1 - 1e-12)).all())
 
 
+def test_ordered_sum_emulation_is_a_sum_and_not_the_sequential_one():
+    """The emulation of the kernels' summation order (S.ordered_stats_emulation) lies within the rounding bound of its own tree around
+    the float64 sum -- every element passes through at most d fp32 additions (16 in its lane, 6 + 3 in the workgroup, one per stride
+    trip and 6 + 3 again in the fold), so |error| <= d u / (1 - d u) * sum |x|, u = 2^-24 -- and from one workgroup's worth of
+    elements on it differs IN BITS from the left-to-right fp32 sum: the GPU test that compares bits with it states an order."""
+    for B, P in S.ORDER_CASES:
+        p, label = S.order_inputs(B, P)
+        emu = S.ordered_stats_emulation(p, label)
+        cols = (torch.clamp(p, min=S.LO, max=S.HI), label)
+        nblk = -(-P // S.ORDER_SPAN)
+        d = 16 + 9 + -(-nblk // 256) + 9
+        gamma = d * 2.0 ** -24 / (1 - d * 2.0 ** -24)
+        for k, x in enumerate(cols):
+            exact = x.double().sum(1).numpy()
+            assert bool((np.abs(emu[:, k].astype(np.float64) - exact) <= gamma * exact).all()), (B, P, k)
+            if P >= 4099:
+                seq = np.cumsum(x.numpy(), axis=1, dtype=np.float32)[:, -1]
+                print((B, P), 'column', k + 1, 'ordered', emu[:, k], 'sequential', seq)
+                # (per sample the two may agree by chance -- label of sample 1 at P = 4100 does; the first sample never does)
+                assert emu[0, k] != seq[0], (B, P, k, emu[:, k], seq)
+
+
 @pytest.mark.parametrize('sigmoid', [True, False])
 @pytest.mark.parametrize('shape', [(2, 8, 1, 1), (2, 16, 3, 5), (1, 32, 9, 11)])
 def test_head_judge_equals_conv2d_and_sigmoid_in_float64(shape, sigmoid):
