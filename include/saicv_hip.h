@@ -723,7 +723,9 @@ int saicv_detr_assign(const float* cost, const unsigned char* valid, int B, int 
  * nn.Conv2d(C, C, K, stride, padding, dilation, groups=C) and its backward: reference
  * SimpleAICV/classification/backbones/van.py:30,68,75 (3x3 / 5x5 / dilated 7x7 of the LKA block) and convformer.py (7x7 of the
  * SepConv mixer).  NHWC activations; weights tap-major wt[K*K][C] in the compute dtype (the [C,1,K,K] parameter transposed),
- * weight gradient dwt[K*K][C] fp32.  dtype 0 bf16 / 1 fp32, fp32 accumulation, C a multiple of 8 (bf16) / 4 (fp32), K <= 8. */
+ * weight gradient dwt[K*K][C] fp32.  dtype 0 bf16 / 1 fp32, fp32 accumulation, C a multiple of 8 (bf16) / 4 (fp32), K <= 8.
+ * All three entries refuse an OH, OW other than (H + 2 pad - dil (K - 1) - 1) / stride + 1 (0 where the kernel does not fit), and
+ * return 0 without a launch when N, OH or OW is 0: nothing is written, nothing is added. */
 int saicv_dwconv2d_fwd(int dtype, const void* x, const void* wt, const float* bias, void* y, int N, int H, int W, int C, int OH,
                        int OW, int K, int stride, int pad, int dil, void* stream);
 int saicv_dwconv2d_dgrad(int dtype, const void* dy, const void* wt, void* dx, int N, int H, int W, int C, int OH, int OW, int K,

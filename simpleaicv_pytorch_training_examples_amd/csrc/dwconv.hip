@@ -276,6 +276,19 @@ int dw_check(const char* who, int dtype, int C, int K, int stride, int pad, int 
     return 0;
 }
 
+// output extent of one axis (0: the kernel does not fit the padded input)
+int dw_out(int H, int K, int stride, int pad, int dil) {
+    const int span = H + 2 * pad - dil * (K - 1) - 1;
+    return span < 0 ? 0 : span / stride + 1;
+}
+
+// every entry holds the caller's OH, OW to the geometry: a pair that does not match would index past a tensor
+int dw_check_out(const char* who, int H, int W, int OH, int OW, int K, int stride, int pad, int dil) {
+    SAICV_REQUIRE(OH == dw_out(H, K, stride, pad, dil) && OW == dw_out(W, K, stride, pad, dil),
+                  "%s: output %d x %d does not match the geometry", who, OH, OW);
+    return 0;
+}
+
 }  // namespace
 
 using saicv::check_launch;
@@ -287,8 +300,8 @@ extern "C" {
 int saicv_dwconv2d_fwd(int dtype, const void* x, const void* wt, const float* bias, void* y, int N, int H, int W, int C, int OH,
                        int OW, int K, int stride, int pad, int dil, void* stream) {
     if (dw_check("dwconv2d_fwd", dtype, C, K, stride, pad, dil)) return -1;
-    SAICV_REQUIRE(OH == (H + 2 * pad - dil * (K - 1) - 1) / stride + 1 && OW == (W + 2 * pad - dil * (K - 1) - 1) / stride + 1,
-                  "dwconv2d_fwd: output %d x %d does not match the geometry", OH, OW);
+    if (dw_check_out("dwconv2d_fwd", H, W, OH, OW, K, stride, pad, dil)) return -1;
+    if (N <= 0 || OH <= 0 || OW <= 0) return 0;             // an empty problem: nothing to launch
     hipStream_t st = (hipStream_t)stream;
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     const size_t items = (size_t)N * OH * ((OW + DW_TW - 1) / DW_TW) * (C / n);
@@ -313,6 +326,8 @@ int saicv_dwconv2d_fwd(int dtype, const void* x, const void* wt, const float* bi
 int saicv_dwconv2d_dgrad(int dtype, const void* dy, const void* wt, void* dx, int N, int H, int W, int C, int OH, int OW, int K,
                          int stride, int pad, int dil, void* stream) {
     if (dw_check("dwconv2d_dgrad", dtype, C, K, stride, pad, dil)) return -1;
+    if (dw_check_out("dwconv2d_dgrad", H, W, OH, OW, K, stride, pad, dil)) return -1;
+    if (N <= 0 || OH <= 0 || OW <= 0) return 0;             // an empty problem: nothing to launch, dx is not written
     hipStream_t st = (hipStream_t)stream;
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     const size_t items = (size_t)N * H * ((W + DW_TW - 1) / DW_TW) * (C / n);
@@ -338,6 +353,8 @@ int saicv_dwconv2d_dgrad(int dtype, const void* dy, const void* wt, void* dx, in
 int saicv_dwconv2d_wgrad(int dtype, const void* dy, const void* x, float* dwt, float* dbias, int N, int H, int W, int C, int OH,
                          int OW, int K, int stride, int pad, int dil, void* stream) {
     if (dw_check("dwconv2d_wgrad", dtype, C, K, stride, pad, dil)) return -1;
+    if (dw_check_out("dwconv2d_wgrad", H, W, OH, OW, K, stride, pad, dil)) return -1;
+    if (N <= 0 || OH <= 0 || OW <= 0) return 0;             // an empty problem adds nothing (and would ask for a grid of height 0)
     hipStream_t st = (hipStream_t)stream;
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     // lanes = chunks (fastest) x kernel rows: the largest power-of-two chunk count with chunks * K <= 256
