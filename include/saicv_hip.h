@@ -610,6 +610,30 @@ int saicv_pixel_class_terms_fwd(int dtype, const void* logits, const float* labe
 int saicv_pixel_class_terms_bwd(int dtype, const void* logits, const float* label, const float* gterms, size_t rows, int C,
                                 int sigmoid, int form, void* dlogits, void* stream);
 
+/* ---- text recognition (text_recognition/losses.py:21-46 CTCLoss; the arg-max + softmax of its validation loop) ----
+ * logits: T x B rows of C classes (bf16 or fp32), unit stride over the classes, element strides st / sb over t and b (any: the
+ * permuted view of a [B, T, C] tensor is taken as it is).  targets int32 [B, S], input_lengths / target_lengths int32 [B], all in
+ * device memory; entries of targets at or beyond a sample's target length are never read.  Three launches, no atomics, no host
+ * sync: per-row log-sum-exp and the log-probabilities of the blank and the sample's labels; the alpha-beta recursion (one
+ * workgroup per sample) -> nll [B] fp32 and the per-class occupancies; loss [1] fp32 = sum_b w_b nll_b / L_b / B in a fixed order,
+ * w_b = (1 - exp(-nll_b))^gamma when focal != 0, else 1.  zero_infinity: a sample whose labels do not fit its frames (L + repeats >
+ * input length), whose nll is not finite, or that holds a label outside [0, C) or equal to the blank gets nll 0, no loss and a zero
+ * gradient; so does a sample with a NaN logit (or nothing above -inf) in one of its frames.  S <= 1819 (the alpha-beta workgroup's
+ * LDS), gamma >= 1.  ws: saicv_ctc_ws_floats(T, B, S) floats, kept for the backward. */
+size_t saicv_ctc_ws_floats(int T, int B, int S);
+int saicv_ctc_loss_fwd(int dtype, const void* logits, long long st, long long sb, const int* targets, const int* input_lengths,
+                       const int* target_lengths, int T, int B, int S, int C, int blank, int focal, float gamma, float* ws, float* nll,
+                       float* loss, void* stream);
+/* dlogits (dtype of logits, element strides dst / dsb) = gout[0] * dloss/dlogits with gout in device memory; every element of every
+ * row is written exactly once (zeros for t >= input length and for dropped samples) */
+int saicv_ctc_loss_bwd(int dtype, const void* logits, long long st, long long sb, void* dlogits, long long dst, long long dsb,
+                       const int* input_lengths, const int* target_lengths, const float* ws, const float* nll, const float* gout, int T,
+                       int B, int S, int C, int focal, float gamma, void* stream);
+/* index int32 [T, B] = arg-max class of each row (the lowest index among equals), prob fp32 [T, B] = its softmax probability; the
+ * softmax is never stored.  input_lengths may be NULL; rows with t >= input length get index -1, probability 0. */
+int saicv_ctc_greedy(int dtype, const void* logits, long long st, long long sb, const int* input_lengths, int T, int B, int C,
+                     int* index, float* prob, void* stream);
+
 /* Streaming attention (any Nq / Nk, head dim 32 or 64, separate q / k / v with strides).
  * Replaces SAM Attention.forward + add_decomposed_rel_pos (reference interactive_segmentation/models/
  * segment_anything/image_encoder.py:116-184) and DETR's nn.MultiheadAttention calls with a float

@@ -262,6 +262,12 @@ SIGNATURES = {
     'saicv_pixel_class_terms_lane_max_classes': (c_int, []),
     'saicv_pixel_class_terms_fwd': (c_int, [c_int, _P, _P, c_size_t, c_int, c_int, c_int, _P, _P, _P]),
     'saicv_pixel_class_terms_bwd': (c_int, [c_int, _P, _P, _P, c_size_t, c_int, c_int, c_int, _P, _P]),
+    'saicv_ctc_ws_floats': (c_size_t, [c_int, c_int, c_int]),
+    'saicv_ctc_loss_fwd': (c_int, [c_int, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
+                                   c_int, c_float, _P, _P, _P, _P]),
+    'saicv_ctc_loss_bwd': (c_int, [c_int, _P, ctypes.c_longlong, ctypes.c_longlong, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P,
+                                   _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P]),
+    'saicv_ctc_greedy': (c_int, [c_int, _P, ctypes.c_longlong, ctypes.c_longlong, _P, c_int, c_int, c_int, _P, _P, _P]),
     'saicv_attention_stream_fwd': (c_int, [c_int, c_int, _PA, _P]),
     'saicv_attention_stream_bwd': (c_int, [c_int, c_int, _PA, _P]),
 }

@@ -671,6 +671,23 @@ int saicv_pixel_class_terms_bwd(int dtype, const void* logits, const float* labe
                                 int sigmoid, int form, void* dlogits, void* stream) {
     return pixel_class_terms_bwd(dtype, logits, label, gterms, rows, C, sigmoid, form, dlogits, S(stream));
 }
+size_t saicv_ctc_ws_floats(int T, int B, int Sx) { return ctc_ws_floats(T, B, Sx); }
+int saicv_ctc_loss_fwd(int dtype, const void* logits, long long st, long long sb, const int* targets, const int* input_lengths,
+                       const int* target_lengths, int T, int B, int Sx, int C, int blank, int focal, float gamma, float* ws, float* nll,
+                       float* loss, void* stream) {
+    return ctc_loss_fwd(dtype, logits, st, sb, targets, input_lengths, target_lengths, T, B, Sx, C, blank, focal, gamma, ws, nll, loss,
+                        S(stream));
+}
+int saicv_ctc_loss_bwd(int dtype, const void* logits, long long st, long long sb, void* dlogits, long long dst, long long dsb,
+                       const int* input_lengths, const int* target_lengths, const float* ws, const float* nll, const float* gout, int T,
+                       int B, int Sx, int C, int focal, float gamma, void* stream) {
+    return ctc_loss_bwd(dtype, logits, st, sb, dlogits, dst, dsb, input_lengths, target_lengths, ws, nll, gout, T, B, Sx, C, focal,
+                        gamma, S(stream));
+}
+int saicv_ctc_greedy(int dtype, const void* logits, long long st, long long sb, const int* input_lengths, int T, int B, int C,
+                     int* index, float* prob, void* stream) {
+    return ctc_greedy(dtype, logits, st, sb, input_lengths, T, B, C, index, prob, S(stream));
+}
 int saicv_attention_stream_fwd(int dtype, int D, const saicv_attn_desc* desc, void* stream) {
     if (!desc) { set_error("attention_stream: null descriptor"); return -1; }
     return attention_stream(dtype, D, 0, desc, S(stream));

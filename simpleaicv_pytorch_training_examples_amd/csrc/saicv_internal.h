@@ -155,6 +155,15 @@ int pixel_class_terms_fwd(int dtype, const void* logits, const float* label, siz
                           float* partial, float* terms, hipStream_t st);
 int pixel_class_terms_bwd(int dtype, const void* logits, const float* label, const float* gterms, size_t rows, int C, int sigmoid,
                           int form, void* dlogits, hipStream_t st);
+// ctc.hip: strides in elements; targets / lengths int32 in device memory
+size_t ctc_ws_floats(int T, int B, int S);
+int ctc_loss_fwd(int dtype, const void* logits, long long st, long long sb, const int* targets, const int* in_len, const int* tg_len,
+                 int T, int B, int S, int C, int blank, int focal, float gamma, float* ws, float* nll, float* loss, hipStream_t s);
+int ctc_loss_bwd(int dtype, const void* logits, long long st, long long sb, void* dlogits, long long dst, long long dsb,
+                 const int* in_len, const int* tg_len, const float* ws, const float* nll, const float* gout, int T, int B, int S, int C,
+                 int focal, float gamma, hipStream_t s);
+int ctc_greedy(int dtype, const void* logits, long long st, long long sb, const int* in_len, int T, int B, int C, int* index,
+               float* prob, hipStream_t s);
 // attn_stream.hip: which = 0 forward, 1 dQ pass, 2 dK/dV pass; desc = const saicv_attn_desc*
 int attention_stream(int dtype, int D, int which, const void* desc, hipStream_t st);
 

@@ -1857,6 +1857,111 @@ def pixel_class_terms(logits, label, logit_type='softmax', form='auto'):
     return terms
 
 
+def _ctc_int(x, who):
+    """lengths / targets -> int32, contiguous, on the device (a device-side cast: the reference passes trans_targets.float())"""
+    if x.dtype == torch.bool or x.is_complex():
+        raise ValueError(f'{who}: integer or floating tensor expected, got {x.dtype}')
+    return x.to(torch.int32).contiguous()
+
+
+def _ctc_rows(logits, who):
+    if logits.dim() != 3:
+        raise ValueError(f'{who} expects [T, B, C] logits, got {tuple(logits.shape)}')
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f'{who}: bf16 or fp32 logits, got {logits.dtype}')
+    if logits.shape[2] > 1 and logits.stride(2) != 1:
+        # no silent copy: at [64, 256, 12113] it would be the 0.4 - 0.8 GB this op exists to avoid
+        raise ValueError(f'{who}: the class axis must have unit stride (t and b may have any), got strides {logits.stride()}; '
+                         f'pass a view of a tensor whose last dimension is the classes')
+    return logits
+
+
+class CTCLossFn(torch.autograd.Function):
+    """The reference's text-recognition CTCLoss (SimpleAICV/text_recognition/losses.py:21-46) in three launches forward and one
+    backward (csrc/ctc.hip), on the [T, B, C] logits in their own dtype and strides: no fp32 copy, no log-softmax tensor.  Saved for
+    the backward: the per-row log-sum-exp, the compact label log-probabilities and the per-class occupancies (T x B x (1 + S)
+    floats each) -- not a dense gradient.  All sums are ordered; dL/dloss is read on the device."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, input_lengths, target_lengths, blank, focal, gamma):
+        L, dev = lib(), logits.device
+        t, b, c = logits.shape
+        s = targets.shape[1]
+        ws = torch.empty(L.saicv_ctc_ws_floats(t, b, s), dtype=torch.float32, device=dev)
+        nll = torch.empty(b, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        t0 = KernelTimer.begin('ctc_loss')
+        check(L.saicv_ctc_loss_fwd(dtype_code(logits.dtype), ptr(logits), logits.stride(0), logits.stride(1), ptr(targets),
+                                   ptr(input_lengths), ptr(target_lengths), t, b, s, c, blank, focal, gamma, ptr(ws), ptr(nll),
+                                   ptr(loss), stream()), 'ctc_loss_fwd')
+        KernelTimer.end(t0, 'ctc_loss', 0, t * b * c * logits.element_size())
+        ctx.save_for_backward(logits, input_lengths, target_lengths, ws, nll)
+        ctx.geom = (s, focal, gamma)
+        ctx.mark_non_differentiable(nll)
+        return loss, nll
+
+    @staticmethod
+    def backward(ctx, gout, _gnll):
+        logits, input_lengths, target_lengths, ws, nll = ctx.saved_tensors
+        s, focal, gamma = ctx.geom
+        t, b, c = logits.shape
+        gout = gout.float().contiguous()
+        dlog = torch.empty_like(logits)                      # preserves the strides of the permuted [B, T, C] view
+        if dlog.stride(2) != 1:
+            dlog = torch.empty(logits.shape, dtype=logits.dtype, device=logits.device)
+        t0 = KernelTimer.begin('ctc_loss')
+        check(lib().saicv_ctc_loss_bwd(dtype_code(logits.dtype), ptr(logits), logits.stride(0), logits.stride(1), ptr(dlog),
+                                       dlog.stride(0), dlog.stride(1), ptr(input_lengths), ptr(target_lengths), ptr(ws), ptr(nll),
+                                       ptr(gout), t, b, s, c, focal, gamma, stream()), 'ctc_loss_bwd')
+        KernelTimer.end(t0, 'ctc_loss', 0, 2 * t * b * c * logits.element_size())
+        return dlog, None, None, None, None, None, None
+
+
+def ctc_loss(logits, targets, input_lengths, target_lengths, blank, focal_gamma=None):
+    """logits [T, B, C] bf16 or fp32 with unit stride over C (any strides over T and B: the permuted view of the model's [B, T, C]
+    output is used as it is); targets [B, S], input_lengths [B], target_lengths [B]: integer or floating device tensors.
+    -> (loss, nll): loss = sum_b w_b nll_b / target_length_b / B with w_b = (1 - exp(-nll_b)) ** focal_gamma (1 when focal_gamma is
+    None), the reference's CTCLoss; nll [B] fp32, detached.  zero_infinity: a sample whose labels do not fit its frames (or with a
+    label outside [0, C) or equal to the blank) has nll 0, adds no loss and gets a zero gradient; entries of targets at or beyond
+    a sample's target length are never used.  No host read: the call can be captured."""
+    require_gpu(logits, targets, input_lengths, target_lengths)
+    logits = _ctc_rows(logits, 'ctc_loss')
+    t, b, c = logits.shape
+    if targets.dim() != 2 or targets.shape[0] != b or input_lengths.numel() != b or target_lengths.numel() != b:
+        raise ValueError(f'ctc_loss: batch {b}, targets {tuple(targets.shape)}, lengths {input_lengths.numel()} / '
+                         f'{target_lengths.numel()}')
+    if not 0 <= int(blank) < c:
+        raise ValueError(f'ctc_loss: blank {blank} outside [0, {c})')
+    focal = focal_gamma is not None
+    if focal and not float(focal_gamma) >= 1.0:
+        raise ValueError(f'ctc_loss: focal_gamma {focal_gamma}; at least 1 (the derivative holds (1 - p) ** (gamma - 1))')
+    return CTCLossFn.apply(logits, _ctc_int(targets, 'ctc_loss'), _ctc_int(input_lengths.reshape(-1), 'ctc_loss'),
+                           _ctc_int(target_lengths.reshape(-1), 'ctc_loss'), int(blank), int(focal),
+                           float(focal_gamma) if focal else 0.0)
+
+
+def ctc_greedy(logits, input_lengths=None):
+    """logits [T, B, C] (as for ctc_loss) -> (index int32 [T, B], prob fp32 [T, B]): each frame's arg-max class (the lowest index
+    among equals) and its softmax probability -- outputs.max(dim=2) and F.softmax(outputs, dim=2).max(dim=2) of the reference's
+    validation loop without the softmax tensor.  Frames at or beyond input_lengths[b] get index -1 and probability 0."""
+    require_gpu(logits)
+    logits = _ctc_rows(logits.detach(), 'ctc_greedy')
+    t, b, c = logits.shape
+    lens = None
+    if input_lengths is not None:
+        require_gpu(input_lengths)
+        if input_lengths.numel() != b:
+            raise ValueError(f'ctc_greedy: batch {b} but {input_lengths.numel()} input lengths')
+        lens = _ctc_int(input_lengths.reshape(-1), 'ctc_greedy')
+    index = torch.empty((t, b), dtype=torch.int32, device=logits.device)
+    prob = torch.empty((t, b), dtype=torch.float32, device=logits.device)
+    t0 = KernelTimer.begin('ctc_greedy')
+    check(lib().saicv_ctc_greedy(dtype_code(logits.dtype), ptr(logits), logits.stride(0), logits.stride(1),
+                                 ptr(lens), t, b, c, ptr(index), ptr(prob), stream()), 'ctc_greedy')
+    KernelTimer.end(t0, 'ctc_greedy', 0, t * b * c * logits.element_size())
+    return index, prob
+
+
 class CpfeConvsFn(torch.autograd.Function):
     """x [N*H*W, Cin], W_all [(1 + 9 nb) P, Cin] -> the concatenated CPFE block output [N, (1 + nb) P, H, W] in `dtype`, NHWC
     memory: LinearFn's GEMM with fp32 output (Z), then the tap gather of csrc/semseg.hip.  One node for both, so that the
