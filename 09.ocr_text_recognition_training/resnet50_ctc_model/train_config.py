@@ -28,7 +28,10 @@ class config:
     # all char + '[CTCblank]' = 12111 + 1 = 12112; the model has one more output, the garbage class
     num_classes = converter.num_classes
 
-    model = CTCModel(backbone_type=os.environ.get('SAICV_OCR_BACKBONE', 'resnet50backbone'), planes=512, num_classes=num_classes + 1)
+    # rnn_route 'fused': ops.lstm instead of nn.LSTM -- the faster route at this shape, eagerly and in the captured step
+    # (profiles/ocr_lstm.json); checkpoints are the same on either route
+    model = CTCModel(backbone_type=os.environ.get('SAICV_OCR_BACKBONE', 'resnet50backbone'), planes=512, num_classes=num_classes + 1,
+                     rnn_route='fused')
 
     trained_model_path = ''
     load_state_dict(trained_model_path, model)

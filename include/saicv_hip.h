@@ -634,6 +634,21 @@ int saicv_ctc_loss_bwd(int dtype, const void* logits, long long st, long long sb
 int saicv_ctc_greedy(int dtype, const void* logits, long long st, long long sb, const int* input_lengths, int T, int B, int C,
                      int* index, float* prob, void* stream);
 
+/* One bidirectional LSTM layer's recurrence (nn.LSTM: one layer, batch_first, zero initial state, gate order i, f, g, o; csrc/lstm.hip).
+ * The input projection and every parameter / input gradient are GEMMs on the entry points above; these two walk T.  H a multiple of
+ * 32 in 32 .. 1024, any B >= 1 and T >= 1; both directions in one launch, no atomics, nothing read back.
+ * gates [B * T][8H] fp32: on entry x W_ih^T + b_ih + b_hh with the forward direction's 4H columns (i, f, g, o) before the reverse
+ * direction's; on exit the activated gates, in place (saved for the backward).  whh: both directions' W_hh [4H][H] in dtype, in
+ * the order the kernel streams its MFMA fragments, [2][H / 16][chunks of 64 bytes of a row][4 gates][64 lanes][16 bytes]: lane l of
+ * slice s, chunk k, gate g holds the 16-byte piece l >> 4 of chunk k of row g H + 16 s + (l & 15).  y [B][T][2H] in dtype
+ * (forward half, then reverse half, as nn.LSTM orders them), c [B][T][2H] fp32 (saved for the backward). */
+int saicv_lstm_fwd(int dtype, float* gates, const void* whh, void* y, float* c, int B, int T, int H, void* stream);
+/* dy [B][T][2H] in dtype; gates and c as the forward left them; whh_t: both directions' transposed W_hh [H][4H] in dtype, in
+ * fragment order [2][H / 16][chunks of 64 bytes of a row][64 lanes][16 bytes] (row 16 s + (l & 15), piece l >> 4).
+ * dgates [B * T][8H] in dtype = dL / d(pre-activations), every element written once: dW_ih, dW_hh, db and dx are GEMMs over it. */
+int saicv_lstm_bwd(int dtype, const void* dy, const float* gates, const float* c, const void* whh_t, void* dgates, int B, int T, int H,
+                   void* stream);
+
 /* Streaming attention (any Nq / Nk, head dim 32 or 64, separate q / k / v with strides).
  * Replaces SAM Attention.forward + add_decomposed_rel_pos (reference interactive_segmentation/models/
  * segment_anything/image_encoder.py:116-184) and DETR's nn.MultiheadAttention calls with a float

@@ -17,14 +17,15 @@ __all__ = [
 
 class CTCModel(nn.Module):
 
-    def __init__(self, backbone_type, backbone_pretrained_path='', planes=256, num_classes=12114, use_gradient_checkpoint=False):
+    def __init__(self, backbone_type, backbone_pretrained_path='', planes=256, num_classes=12114, use_gradient_checkpoint=False,
+                 rnn_route='library'):
         super(CTCModel, self).__init__()
         self.use_gradient_checkpoint = use_gradient_checkpoint
         self.backbone = backbones.__dict__[backbone_type](**{
             'pretrained_path': backbone_pretrained_path,
             'use_gradient_checkpoint': use_gradient_checkpoint,
         })
-        self.encoder = BiLSTMEncoder(inplanes=self.backbone.out_channels[-1], hidden_planes=planes)
+        self.encoder = BiLSTMEncoder(inplanes=self.backbone.out_channels[-1], hidden_planes=planes, rnn_route=rnn_route)
         self.predictor = CTCPredictor(inplanes=planes, hidden_planes=planes, num_classes=num_classes)
 
     def forward(self, x):

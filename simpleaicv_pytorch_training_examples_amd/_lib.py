@@ -268,6 +268,8 @@ SIGNATURES = {
     'saicv_ctc_loss_bwd': (c_int, [c_int, _P, ctypes.c_longlong, ctypes.c_longlong, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P,
                                    _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P]),
     'saicv_ctc_greedy': (c_int, [c_int, _P, ctypes.c_longlong, ctypes.c_longlong, _P, c_int, c_int, c_int, _P, _P, _P]),
+    'saicv_lstm_fwd': (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    'saicv_lstm_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     'saicv_attention_stream_fwd': (c_int, [c_int, c_int, _PA, _P]),
     'saicv_attention_stream_bwd': (c_int, [c_int, c_int, _PA, _P]),
 }

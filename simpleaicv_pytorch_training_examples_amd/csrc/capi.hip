@@ -671,6 +671,13 @@ int saicv_pixel_class_terms_bwd(int dtype, const void* logits, const float* labe
                                 int sigmoid, int form, void* dlogits, void* stream) {
     return pixel_class_terms_bwd(dtype, logits, label, gterms, rows, C, sigmoid, form, dlogits, S(stream));
 }
+int saicv_lstm_fwd(int dtype, float* gates, const void* whh, void* y, float* c, int B, int T, int H, void* stream) {
+    return lstm_fwd(dtype, gates, whh, y, c, B, T, H, S(stream));
+}
+int saicv_lstm_bwd(int dtype, const void* dy, const float* gates, const float* c, const void* whh_t, void* dgates, int B, int T, int H,
+                   void* stream) {
+    return lstm_bwd(dtype, dy, gates, c, whh_t, dgates, B, T, H, S(stream));
+}
 size_t saicv_ctc_ws_floats(int T, int B, int Sx) { return ctc_ws_floats(T, B, Sx); }
 int saicv_ctc_loss_fwd(int dtype, const void* logits, long long st, long long sb, const int* targets, const int* input_lengths,
                        const int* target_lengths, int T, int B, int Sx, int C, int blank, int focal, float gamma, float* ws, float* nll,

@@ -155,6 +155,11 @@ int pixel_class_terms_fwd(int dtype, const void* logits, const float* label, siz
                           float* partial, float* terms, hipStream_t st);
 int pixel_class_terms_bwd(int dtype, const void* logits, const float* label, const float* gterms, size_t rows, int C, int sigmoid,
                           int form, void* dlogits, hipStream_t st);
+// lstm.hip: one bidirectional LSTM layer's recurrence.  gates [B * T][8H] fp32 in place (pre-activations in, activated gates out),
+// whh [2][4H][H] / whhT [2][H][4H], y and dy [B][T][2H] and dgates [B * T][8H] in the compute dtype, c [B][T][2H] fp32
+int lstm_fwd(int dtype, float* gates, const void* whh, void* y, float* c, int B, int T, int H, hipStream_t s);
+int lstm_bwd(int dtype, const void* dy, const float* acts, const float* c, const void* whhT, void* dgates, int B, int T, int H,
+             hipStream_t s);
 // ctc.hip: strides in elements; targets / lengths int32 in device memory
 size_t ctc_ws_floats(int T, int B, int S);
 int ctc_loss_fwd(int dtype, const void* logits, long long st, long long sb, const int* targets, const int* in_len, const int* tg_len,

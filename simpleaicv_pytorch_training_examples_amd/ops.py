@@ -1962,6 +1962,155 @@ def ctc_greedy(logits, input_lengths=None):
     return index, prob
 
 
+LSTM_WEIGHT_NAMES = ('weight_ih_l0', 'weight_hh_l0', 'bias_ih_l0', 'bias_hh_l0',
+                     'weight_ih_l0_reverse', 'weight_hh_l0_reverse', 'bias_ih_l0_reverse', 'bias_hh_l0_reverse')
+
+
+def lstm_supports(input_size, hidden_size, dtype):
+    """Whether ops.lstm runs this combination: bf16 or fp32, a hidden size that is a multiple of 32 in 32 .. 1024, an input size
+    that is a multiple of the dtype's 16-byte chunk (8 bf16, 4 fp32)."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return False
+    h, i = int(hidden_size), int(input_size)
+    return 32 <= h <= 1024 and h % 32 == 0 and i >= 1 and i % _lib.epc(dtype) == 0
+
+
+def _lstm_fragments(w, gates):
+    """w [2, gates * H', K] (rows: gate-major) -> the MFMA B fragments in the order csrc/lstm.hip streams them,
+    [2][H' / 16 slices][K chunks of 64 bytes][gates][64 lanes][16 bytes]: lane l of a fragment holds row 16 s + (l & 15), 16-byte
+    piece l >> 4 of the chunk.  One copy; every load instruction of a wave then reads one contiguous KiB."""
+    e = _lib.epc(w.dtype)
+    two, rows, k = w.shape
+    hs = rows // gates
+    v = w.reshape(2, gates, hs // 16, 16, k // (4 * e), 4, e)            # [dir, g, slice, fr, chunk, fq, e]
+    return v.permute(0, 2, 4, 1, 5, 3, 6).contiguous()                   # [dir, slice, chunk, g, fq, fr, e]
+
+
+class LSTMFn(torch.autograd.Function):
+    """One bidirectional nn.LSTM layer (batch_first, zero initial state).  Forward: the input projection of all frames and both
+    directions as ONE GEMM with fp32 output (the stacked W_ih, b_ih + b_hh in the epilogue), then the recurrence of csrc/lstm.hip,
+    which turns the pre-activations into the activated gates in place.  Saved: those gates [B T, 8H] fp32, c [B, T, 2H] fp32, y, x.
+    Backward: the recurrence against the order writes dgates [B T, 8H] in the compute dtype; dx, dW_ih, dW_hh and the bias
+    gradients are GEMMs / column sums over it on the implicit-GEMM kernels (fp32 weight gradients, ordered in deterministic mode)."""
+
+    @staticmethod
+    def forward(ctx, x, wih_f, whh_f, bih_f, bhh_f, wih_r, whh_r, bih_r, bhh_r):
+        L, dev, dt = lib(), x.device, x.dtype
+        b, t, i = x.shape
+        h = whh_f.shape[1]
+        x2 = x.reshape(b * t, i).contiguous()               # a row-strided view (padded out-features in front) is gathered here
+        with torch.no_grad():
+            wih = torch.cat([wih_f, wih_r])                                             # [8H, I]
+            bias = torch.cat([bih_f + bhh_f, bih_r + bhh_r]).float()                    # [8H]
+            whh = torch.stack([whh_f, whh_r]).to(dt)                                    # [2, 4H, H]
+        wf, wd = packed_weight(wih, dt, i, ctx.needs_input_grad[0] and dt != torch.float32, 8 * h)
+        d = _desc(b * t, 1, 1, i, 8 * h, 1, 1, 1, 0, dt)
+        gates = torch.empty((b * t, 8 * h), dtype=torch.float32, device=dev)
+        check(L.saicv_conv2d_fwd(ctypes.byref(d), ptr(x2), ptr(wf), ptr(bias), ptr(gates), 1, 0, 0, stream()), 'lstm input projection')
+        y = torch.empty((b, t, 2 * h), dtype=dt, device=dev)
+        c = torch.empty((b, t, 2 * h), dtype=torch.float32, device=dev)
+        t0 = KernelTimer.begin('lstm_fwd')
+        check(L.saicv_lstm_fwd(dtype_code(dt), ptr(gates), ptr(_lstm_fragments(whh, 4)), ptr(y), ptr(c), b, t, h, stream()),
+              'lstm_fwd')
+        KernelTimer.end(t0, 'lstm_fwd', 16.0 * b * t * h * h, 0)
+        ctx.save_for_backward(x2, whh, gates, c, y)
+        ctx.cfg = (d, wd, wih, (wih_f, wih_r), b, t, i, h)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, whh, gates, c, y = ctx.saved_tensors
+        d, wd, wih, wih_dirs, b, t, i, h = ctx.cfg
+        L, st, dev, dt = lib(), stream(), x2.device, x2.dtype
+        dy = dy.contiguous()
+        if dy.dtype != dt:
+            dy = dy.to(dt)
+        whh_t = _lstm_fragments(whh.transpose(1, 2), 1)                                 # [2, H, 4H] in fragment order: once per call
+        dgates = torch.empty((b * t, 8 * h), dtype=dt, device=dev)
+        t0 = KernelTimer.begin('lstm_bwd')
+        check(L.saicv_lstm_bwd(dtype_code(dt), ptr(dy), ptr(gates), ptr(c), ptr(whh_t), ptr(dgates), b, t, h, st), 'lstm_bwd')
+        KernelTimer.end(t0, 'lstm_bwd', 16.0 * b * t * h * h, 0)
+        need = ctx.needs_input_grad
+        dx = None
+        if need[0] and dt == torch.float32:
+            # fp32 (parity mode): one product per direction and their sum, as the reference's module forms dx -- sums of 4H terms
+            # each, not one of 8H (the fp32 MFMA adds its K terms in one chain: at H = 512 the 8H chain alone used up the 4 x bound
+            # of tests/lstm_common.py)
+            d4 = _desc(b * t, 1, 1, i, 4 * h, 1, 1, 1, 0, dt)
+            part = None
+            for k, w_dir in enumerate(wih_dirs):
+                _, wd_dir = packed_weight(w_dir, dt, i, True, 4 * h)
+                dg = dgates[:, 4 * h * k:4 * h * (k + 1)].contiguous()
+                dx = torch.empty((b * t, i), dtype=dt, device=dev)
+                if part is None:
+                    check(L.saicv_conv2d_dgrad(ctypes.byref(d4), ptr(dg), ptr(wd_dir), ptr(dx), st), 'lstm dx')
+                else:
+                    check(L.saicv_conv2d_dgrad_add(ctypes.byref(d4), ptr(dg), ptr(wd_dir), ptr(part), ptr(dx), st), 'lstm dx')
+                part = dx
+            dx = dx.view(b, t, i)
+        elif need[0]:
+            # bf16: ONE product over both directions' 8H columns, so that dx is rounded to bf16 once
+            if wd is None:
+                _, wd = packed_weight(wih, dt, i, True, 8 * h)
+            dx = torch.empty((b * t, i), dtype=dt, device=dev)
+            check(L.saicv_conv2d_dgrad(ctypes.byref(d), ptr(dgates), ptr(wd), ptr(dx), st), 'lstm dx')
+            dx = dx.view(b, t, i)
+        dwih_f = dwih_r = dwhh_f = dwhh_r = db_f = db_r = None
+        if need[1] or need[5]:
+            dwih = torch.zeros((8 * h, i), dtype=torch.float32, device=dev)
+            check(L.saicv_conv2d_wgrad(ctypes.byref(d), ptr(dgates), ptr(x2), ptr(dwih), st), 'lstm dW_ih')
+            dwih_f, dwih_r = dwih[:4 * h], dwih[4 * h:]
+        if need[2] or need[6]:
+            # h_{t-1} of each direction: y shifted one step in the direction's order, zero at its first step.  One GEMM over both
+            # directions' columns; the two diagonal blocks of the [8H, 2H] product are the gradients
+            hp = torch.zeros((b, t, 2 * h), dtype=dt, device=dev)
+            if t > 1:
+                hp[:, 1:, :h] = y[:, :-1, :h]
+                hp[:, :-1, h:] = y[:, 1:, h:]
+            d2 = _desc(b * t, 1, 1, 2 * h, 8 * h, 1, 1, 1, 0, dt)
+            dwhh = torch.zeros((8 * h, 2 * h), dtype=torch.float32, device=dev)
+            check(L.saicv_conv2d_wgrad(ctypes.byref(d2), ptr(dgates), ptr(hp), ptr(dwhh), st), 'lstm dW_hh')
+            dwhh_f, dwhh_r = dwhh[:4 * h, :h], dwhh[4 * h:, h:]
+        if any(need[k] for k in (3, 4, 7, 8)):
+            db = torch.zeros(8 * h, dtype=torch.float32, device=dev)
+            check(L.saicv_colsum(dtype_code(dt), ptr(dgates), b * t, 8 * h, ptr(db), st), 'lstm db')
+            db_f, db_r = db[:4 * h], db[4 * h:]
+        # (b_ih and b_hh enter as their sum: both get the column sums, each its own tensor)
+        return (dx, dwih_f, dwhh_f, db_f, None if db_f is None else db_f.clone(), dwih_r, dwhh_r, db_r,
+                None if db_r is None else db_r.clone())
+
+
+def lstm(x, weights, bidirectional=True):
+    """x [B, T, I] bf16 or fp32 (the last axis dense; rows may be strided) -> y [B, T, 2H]: torch.nn.LSTM(I, H, num_layers=1,
+    batch_first=True, bidirectional=True) with zero initial state, no dropout, no projection.  weights: the module's tensors under
+    its own names (a dict, e.g. dict(rnn.named_parameters())), or the eight of them in nn.LSTM's order.  See lstm_supports();
+    anything else raises ValueError before a launch.  No host read: the call can be captured."""
+    if not bidirectional:
+        raise ValueError('lstm: only the bidirectional layer is built')
+    if isinstance(weights, dict):
+        missing = [n for n in LSTM_WEIGHT_NAMES if n not in weights]
+        if missing:
+            raise ValueError(f'lstm: weights lack {missing}')
+        ws = [weights[n] for n in LSTM_WEIGHT_NAMES]
+    else:
+        ws = list(weights)
+        if len(ws) != 8:
+            raise ValueError(f'lstm: eight tensors expected (nn.LSTM order, both directions, both biases), got {len(ws)}')
+    if x.dim() != 3 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f'lstm expects [B, T, I] with B, T >= 1, got {tuple(x.shape)}')
+    if x.shape[2] > 1 and x.stride(2) != 1:
+        raise ValueError(f'lstm: the feature axis must have unit stride, got strides {x.stride()}')
+    i, h = x.shape[2], ws[1].shape[1]
+    if not lstm_supports(i, h, x.dtype):
+        raise ValueError(f'lstm: input size {i}, hidden size {h}, {x.dtype} is not supported (lstm_supports)')
+    for k in (0, 4):
+        if tuple(ws[k].shape) != (4 * h, i) or tuple(ws[k + 1].shape) != (4 * h, h) or tuple(ws[k + 2].shape) != (4 * h,) \
+                or tuple(ws[k + 3].shape) != (4 * h,):
+            raise ValueError(f'lstm: weight shapes {[tuple(w.shape) for w in ws[k:k + 4]]} for input size {i}, hidden size {h}')
+    require_gpu(x, *ws)
+    return LSTMFn.apply(x, *ws)
+
+
 class CpfeConvsFn(torch.autograd.Function):
     """x [N*H*W, Cin], W_all [(1 + 9 nb) P, Cin] -> the concatenated CPFE block output [N, (1 + nb) P, H, W] in `dtype`, NHWC
     memory: LinearFn's GEMM with fp32 output (Z), then the tap gather of csrc/semseg.hip.  One node for both, so that the

@@ -56,6 +56,9 @@ def set_seed(seed):
     from .. import ops
     if os.environ.get('SAICV_DETERMINISTIC', '1') != '0':
         ops.set_deterministic(True)
+        # the few convolutions that run through torch (the (3, 1) stride-(2, 1) ones of the text-recognition backbones) get torch's
+        # deterministic kernels, the reference's own line: their weight gradient is not repeatable run to run otherwise
+        torch.backends.cudnn.deterministic = True
         if os.environ.get('SAICV_BN_INLINE') == '1':
             ops.BN_INLINE = True
     elif os.environ.get('SAICV_BN_INLINE') is None:
