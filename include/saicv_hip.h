@@ -590,6 +590,32 @@ int saicv_lap_level_bwd(const float* src, const float* alpha, const float* trima
                         const float* table, const float* gnext, const float* topcur, const float* gs, const float* gtop, float* gcur,
                         void* stream);
 
+/* ---- grouped matting statistics (interactive_segmentation/losses_matting.py: SAMMattingLoss judges M predictions per sample against
+ * one set of targets).  Prediction rows are (b, m): global_preds [B][M][3][P], local_preds and fused_preds [B][M][P], contiguous, in
+ * dtype (bf16 or fp32); alpha, trimap [B][P] and image, fg, bg [B][3][P] fp32 are rows b and are loaded once per pixel for all M.
+ * stats [B][M][8] = (bce sum, IoU-term sum (smooth 1e-4), sum sqrt(((clamp(local) - alpha) w)^2 + 1e-12), sum w,
+ * sum sqrt((clamp(fused) - alpha)^2 + 1e-12), composition sum, count [clamp(fused) > thr & alpha > thr], count of the union);
+ * ordered two-pass sums, no atomics.  partial: saicv_group_matting_ws_floats floats. */
+size_t saicv_group_matting_ws_floats(int B, int M, size_t P);
+int saicv_group_matting_stats_fwd(int dtype, const void* global_preds, const void* local_preds, const void* fused_preds,
+                                  const float* alpha, const float* trimap, const float* image, const float* fg, const float* bg, int B,
+                                  int M, size_t P, float mask_threshold, float* partial, float* stats, void* stream);
+/* gstats [B][M][8] = dL/dstats (columns 3, 6 and 7 carry no gradient).  Every element of dglobal, dlocal and dfused (dtype) is
+ * written once, exactly 0 outside the clamp; a row whose coefficients are all zero is zero-filled without reading its predictions. */
+int saicv_group_matting_stats_bwd(int dtype, const void* global_preds, const void* local_preds, const void* fused_preds,
+                                  const float* alpha, const float* trimap, const float* image, const float* fg, const float* bg,
+                                  const float* gstats, int B, int M, size_t P, void* dglobal, void* dlocal, void* dfused,
+                                  void* stream);
+/* Level 0 of saicv_lap_level_fwd for R = B * group rows of src [R][h][w] against alpha / trimap [B][h][w]: row r reads the targets
+ * of sample r / group.  The coarser levels run on saicv_lap_level_fwd with B = R. */
+int saicv_lap_level0_group_fwd(const float* src, const float* alpha, const float* trimap, int group, int R, int h, int w,
+                               const float* table, float* next, float* partial, float* sum_e, void* stream);
+/* saicv_lap_level_bwd on R rows with gall [nsum][R] = every dL/dsums of the pyramid: a row whose nsum entries are all zero takes no
+ * pass -- level 0 writes zeros without reading src, a coarser level leaves the row of gcur unwritten (nothing reads it). */
+int saicv_lap_level_group_bwd(const float* src, const float* alpha, const float* trimap, int level0, int group, int R, int h, int w,
+                              const float* table, const float* gnext, const float* topcur, const float* gs, const float* gtop,
+                              const float* gall, int nsum, float* gcur, void* stream);
+
 /* ---- face and human parsing (human_parsing/losses.py:13-149 CELoss, MultiClassBCELoss, IoULoss, DiceLoss; face_parsing/losses.py
  *      holds the same four) ----
  * One pass over logits [rows][C] (bf16 or fp32, the NHWC view of the prediction, 16-byte aligned, 2 <= C <= 256) and labels fp32

@@ -258,6 +258,11 @@ SIGNATURES = {
     'saicv_lap_level_ws_floats': (c_size_t, [c_int] * 3),
     'saicv_lap_level_fwd': (c_int, [_P, _P, _P] + [c_int] * 4 + [POINTER(ctypes.c_float)] + [_P] * 5),
     'saicv_lap_level_bwd': (c_int, [_P, _P, _P] + [c_int] * 4 + [POINTER(ctypes.c_float)] + [_P] * 6),
+    'saicv_group_matting_ws_floats': (c_size_t, [c_int, c_int, c_size_t]),
+    'saicv_group_matting_stats_fwd': (c_int, [c_int] + [_P] * 8 + [c_int, c_int, c_size_t, ctypes.c_float, _P, _P, _P]),
+    'saicv_group_matting_stats_bwd': (c_int, [c_int] + [_P] * 9 + [c_int, c_int, c_size_t, _P, _P, _P, _P]),
+    'saicv_lap_level0_group_fwd': (c_int, [_P, _P, _P] + [c_int] * 4 + [POINTER(ctypes.c_float)] + [_P] * 4),
+    'saicv_lap_level_group_bwd': (c_int, [_P, _P, _P] + [c_int] * 5 + [POINTER(ctypes.c_float)] + [_P] * 5 + [c_int, _P, _P]),
     'saicv_pixel_class_terms_ws_floats': (c_size_t, [c_size_t]),
     'saicv_pixel_class_terms_lane_max_classes': (c_int, []),
     'saicv_pixel_class_terms_fwd': (c_int, [c_int, _P, _P, c_size_t, c_int, c_int, c_int, _P, _P, _P]),

@@ -661,6 +661,32 @@ int saicv_lap_level_bwd(const float* src, const float* alpha, const float* trima
     if (!table) { set_error("lap_level_bwd: null weight table"); return -1; }
     return lap_level_bwd(src, alpha, trimap, level0, B, h, w, table, gnext, topcur, gs, gtop, gcur, S(stream));
 }
+size_t saicv_group_matting_ws_floats(int B, int M, size_t P) { return group_matting_ws_floats(B, M, P); }
+int saicv_group_matting_stats_fwd(int dtype, const void* global_preds, const void* local_preds, const void* fused_preds,
+                                  const float* alpha, const float* trimap, const float* image, const float* fg, const float* bg, int B,
+                                  int M, size_t P, float mask_threshold, float* partial, float* stats, void* stream) {
+    return group_matting_stats_fwd(dtype, global_preds, local_preds, fused_preds, alpha, trimap, image, fg, bg, B, M, P,
+                                   mask_threshold, partial, stats, S(stream));
+}
+int saicv_group_matting_stats_bwd(int dtype, const void* global_preds, const void* local_preds, const void* fused_preds,
+                                  const float* alpha, const float* trimap, const float* image, const float* fg, const float* bg,
+                                  const float* gstats, int B, int M, size_t P, void* dglobal, void* dlocal, void* dfused,
+                                  void* stream) {
+    return group_matting_stats_bwd(dtype, global_preds, local_preds, fused_preds, alpha, trimap, image, fg, bg, gstats, B, M, P,
+                                   dglobal, dlocal, dfused, S(stream));
+}
+int saicv_lap_level0_group_fwd(const float* src, const float* alpha, const float* trimap, int group, int R, int h, int w,
+                               const float* table, float* next, float* partial, float* sum_e, void* stream) {
+    if (!table) { set_error("lap_level0_group_fwd: null weight table"); return -1; }
+    return lap_level0_group_fwd(src, alpha, trimap, group, R, h, w, table, next, partial, sum_e, S(stream));
+}
+int saicv_lap_level_group_bwd(const float* src, const float* alpha, const float* trimap, int level0, int group, int R, int h, int w,
+                              const float* table, const float* gnext, const float* topcur, const float* gs, const float* gtop,
+                              const float* gall, int nsum, float* gcur, void* stream) {
+    if (!table) { set_error("lap_level_group_bwd: null weight table"); return -1; }
+    return lap_level_group_bwd(src, alpha, trimap, level0, group, R, h, w, table, gnext, topcur, gs, gtop, gall, nsum, gcur,
+                               S(stream));
+}
 size_t saicv_pixel_class_terms_ws_floats(size_t rows) { return pixel_class_terms_ws_floats(rows); }
 int saicv_pixel_class_terms_lane_max_classes(void) { return pixel_class_terms_lane_max_classes(); }
 int saicv_pixel_class_terms_fwd(int dtype, const void* logits, const float* label, size_t rows, int C, int sigmoid, int form,

@@ -350,6 +350,229 @@ __global__ __launch_bounds__(256) void composition_l1_kernel(const float* __rest
     if (!BWD) block_sums<1>(s, out + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
+// ------------------------------------------------------------------------------------------------ grouped statistics
+// SAM matting (interactive_segmentation/losses_matting.py): M predictions per sample are judged against ONE set of targets.
+// Prediction rows are (b, m), contiguous planes [B][M][3][P] / [B][M][P] in T (fp32 or bf16); targets are rows b.  A workgroup owns
+// 4096 pixels of a sample: the 11 target values of a pixel are loaded once and serve up to GM_M masks (blockIdx.z takes the next
+// GM_M when M is larger).  Column j of a (b, m) row:
+//   0 bce sum, 1 IoU-term sum, 2 local alpha sum, 3 sum w, 4 fused alpha sum, 5 composition sum,
+//   6 count [clamp(fused) > thr & alpha > thr], 7 count of their union (whole numbers, exact in fp32 below 2^24 pixels)
+constexpr int GM_M = 4, GM_K = 8;
+
+struct GmTargets {
+    const float *alpha, *trimap, *image, *fg, *bg;      // rows b: [P], [P], [3][P] each
+};
+
+template <typename T> DEVINL f32x4 gm_ld4(const T* p);
+template <> DEVINL f32x4 gm_ld4<float>(const float* p) { return mt_ld4(p); }
+template <> DEVINL f32x4 gm_ld4<bf16_t>(const bf16_t* p) {
+    const bf16x4 v = __builtin_nontemporal_load(reinterpret_cast<const bf16x4*>(p));
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = (float)v[j];
+    return o;
+}
+template <typename T> DEVINL void gm_st4(T* p, f32x4 v);
+template <> DEVINL void gm_st4<float>(float* p, f32x4 v) { mt_st4(p, v); }
+template <> DEVINL void gm_st4<bf16_t>(bf16_t* p, f32x4 v) {
+    bf16x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = (bf16_t)v[j];
+    *reinterpret_cast<bf16x4*>(p) = o;
+}
+
+// one pixel of one mask: the same expressions, in the same order, as tri_add / alpha_add / comp_px
+DEVINL void gm_add(const float (&gp)[3], float lp, float fp, float a, float tv, const float (&f)[3], const float (&b)[3],
+                   const float (&im)[3], float thr, float* s) {
+    float two[2] = {0.f, 0.f};
+    tri_add(gp, tv, 1e-4f, two);
+    s[0] += two[0];
+    s[1] += two[1];
+    const float w = tv == 128.f ? 1.f : 0.f;
+    const float dl = (mt_clamp(lp) - a) * w;
+    s[2] += sqrtf(dl * dl + MT_EPS);
+    s[3] += w;
+    const float df = mt_clamp(fp) - a;
+    s[4] += sqrtf(df * df + MT_EPS);
+    s[5] += comp_px<0>(fp, f, b, im, 0.f);
+    const bool pb = mt_clamp(fp) > thr, ab = a > thr;
+    s[6] += pb && ab ? 1.f : 0.f;
+    s[7] += pb || ab ? 1.f : 0.f;
+}
+
+// grid (blocks of a sample, B, groups of GM_M masks): partial[(b * groups + z)][block][GM_M * GM_K]
+template <typename T>
+__global__ __launch_bounds__(256) void group_stats_fwd_kernel(const T* __restrict__ gpred, const T* __restrict__ lpred,
+                                                              const T* __restrict__ fpred, GmTargets t, size_t P, int M, int vec,
+                                                              float thr, float* __restrict__ partial) {
+    const size_t e0 = (size_t)blockIdx.x * MT_SPAN, e1 = e0 + MT_SPAN < P ? e0 + MT_SPAN : P;
+    const int b = blockIdx.y, m0 = blockIdx.z * GM_M;
+    const float* aa = t.alpha + (size_t)b * P;
+    const float* tm = t.trimap + (size_t)b * P;
+    const float* ii = t.image + (size_t)b * 3 * P;
+    const float* ff = t.fg + (size_t)b * 3 * P;
+    const float* bb = t.bg + (size_t)b * 3 * P;
+    float s[GM_M * GM_K];
+#pragma unroll
+    for (int j = 0; j < GM_M * GM_K; ++j) s[j] = 0.f;
+    if (vec) {
+        for (size_t i = e0 + (size_t)threadIdx.x * 4; i < e1; i += 1024) {
+            const f32x4 av = mt_ld4(aa + i), tv = mt_ld4(tm + i);
+            f32x4 fv[3], bv[3], iv[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                fv[c] = mt_ld4(ff + c * P + i);
+                bv[c] = mt_ld4(bb + c * P + i);
+                iv[c] = mt_ld4(ii + c * P + i);
+            }
+#pragma unroll
+            for (int mm = 0; mm < GM_M; ++mm) {
+                if (m0 + mm >= M) break;
+                const size_t row = (size_t)b * M + m0 + mm;
+                f32x4 gv[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) gv[c] = gm_ld4<T>(gpred + (row * 3 + c) * P + i);
+                const f32x4 lv = gm_ld4<T>(lpred + row * P + i), pv = gm_ld4<T>(fpred + row * P + i);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float gp[3] = {gv[0][j], gv[1][j], gv[2][j]};
+                    const float f[3] = {fv[0][j], fv[1][j], fv[2][j]}, bg[3] = {bv[0][j], bv[1][j], bv[2][j]};
+                    const float im[3] = {iv[0][j], iv[1][j], iv[2][j]};
+                    gm_add(gp, lv[j], pv[j], av[j], tv[j], f, bg, im, thr, s + mm * GM_K);
+                }
+            }
+        }
+    } else {
+        for (size_t i = e0 + threadIdx.x; i < e1; i += 256) {
+            const float a = aa[i], tv = tm[i];
+            const float f[3] = {ff[i], ff[P + i], ff[2 * P + i]}, bg[3] = {bb[i], bb[P + i], bb[2 * P + i]};
+            const float im[3] = {ii[i], ii[P + i], ii[2 * P + i]};
+#pragma unroll
+            for (int mm = 0; mm < GM_M; ++mm) {
+                if (m0 + mm >= M) break;
+                const size_t row = (size_t)b * M + m0 + mm;
+                const float gp[3] = {to_f32(gpred[row * 3 * P + i]), to_f32(gpred[(row * 3 + 1) * P + i]),
+                                     to_f32(gpred[(row * 3 + 2) * P + i])};
+                gm_add(gp, to_f32(lpred[row * P + i]), to_f32(fpred[row * P + i]), a, tv, f, bg, im, thr, s + mm * GM_K);
+            }
+        }
+    }
+    block_sums<GM_M * GM_K>(s, partial + (((size_t)b * gridDim.z + blockIdx.z) * gridDim.x + blockIdx.x) * (GM_M * GM_K));
+}
+
+// one workgroup per (sample, group): stats[b][m][k]
+__global__ __launch_bounds__(256) void group_stats_fold_kernel(const float* __restrict__ partial, int nblk, int M, int groups,
+                                                               float* __restrict__ stats) {
+    const float total = fold_rows<GM_M * GM_K>(partial + (size_t)blockIdx.x * nblk * (GM_M * GM_K), nblk, GM_M * GM_K);
+    const int b = blockIdx.x / groups, m = (blockIdx.x % groups) * GM_M + (int)threadIdx.x / GM_K;
+    if (threadIdx.x < GM_M * GM_K && m < M) stats[((size_t)b * M + m) * GM_K + threadIdx.x % GM_K] = total;
+}
+
+// gstats [B][M][GM_K] = dL/dstats (columns 3, 6 and 7 carry no gradient).  Every element of the three gradients is written once; a
+// row whose five live coefficients are all zero gets zeros and its predictions are not read.
+template <typename T>
+__global__ __launch_bounds__(256) void group_stats_bwd_kernel(const T* __restrict__ gpred, const T* __restrict__ lpred,
+                                                              const T* __restrict__ fpred, GmTargets t,
+                                                              const float* __restrict__ gstats, size_t P, int M, int vec,
+                                                              T* __restrict__ dgpred, T* __restrict__ dlpred, T* __restrict__ dfpred) {
+    const size_t e0 = (size_t)blockIdx.x * MT_SPAN, e1 = e0 + MT_SPAN < P ? e0 + MT_SPAN : P;
+    const int b = blockIdx.y, m0 = blockIdx.z * GM_M;
+    const float* aa = t.alpha + (size_t)b * P;
+    const float* tm = t.trimap + (size_t)b * P;
+    const float* ii = t.image + (size_t)b * 3 * P;
+    const float* ff = t.fg + (size_t)b * 3 * P;
+    const float* bb = t.bg + (size_t)b * 3 * P;
+    float c[GM_M][5];
+    bool live[GM_M], any = false;
+#pragma unroll
+    for (int mm = 0; mm < GM_M; ++mm) {
+        live[mm] = false;
+        if (m0 + mm < M) {
+            const float* g = gstats + ((size_t)b * M + m0 + mm) * GM_K;
+            c[mm][0] = g[0]; c[mm][1] = g[1]; c[mm][2] = g[2]; c[mm][3] = g[4]; c[mm][4] = g[5];
+#pragma unroll
+            for (int j = 0; j < 5; ++j) live[mm] = live[mm] || c[mm][j] != 0.f;
+        }
+        any = any || live[mm];
+    }
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    if (vec) {
+        for (size_t i = e0 + (size_t)threadIdx.x * 4; i < e1; i += 1024) {
+            f32x4 av = zero4, tv = zero4, fv[3], bv[3], iv[3];
+            if (any) {
+                av = mt_ld4(aa + i);
+                tv = mt_ld4(tm + i);
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    fv[ch] = mt_ld4(ff + ch * P + i);
+                    bv[ch] = mt_ld4(bb + ch * P + i);
+                    iv[ch] = mt_ld4(ii + ch * P + i);
+                }
+            }
+#pragma unroll
+            for (int mm = 0; mm < GM_M; ++mm) {
+                if (m0 + mm >= M) break;
+                const size_t row = (size_t)b * M + m0 + mm;
+                f32x4 dg[3] = {zero4, zero4, zero4}, dl = zero4, df = zero4;
+                if (live[mm]) {
+                    f32x4 gv[3];
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) gv[ch] = gm_ld4<T>(gpred + (row * 3 + ch) * P + i);
+                    const f32x4 lv = gm_ld4<T>(lpred + row * P + i), pv = gm_ld4<T>(fpred + row * P + i);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float gp[3] = {gv[0][j], gv[1][j], gv[2][j]};
+                        const float f[3] = {fv[0][j], fv[1][j], fv[2][j]}, bg[3] = {bv[0][j], bv[1][j], bv[2][j]};
+                        const float im[3] = {iv[0][j], iv[1][j], iv[2][j]};
+                        float d[3];
+                        tri_grad(gp, tv[j], 1e-4f, c[mm][0], c[mm][1], d);
+#pragma unroll
+                        for (int ch = 0; ch < 3; ++ch) dg[ch][j] = d[ch];
+                        dl[j] = alpha_grad(lv[j], av[j], tv[j] == 128.f ? 1.f : 0.f, c[mm][2]);
+                        df[j] = alpha_grad(pv[j], av[j], 1.f, c[mm][3]) + comp_px<1>(pv[j], f, bg, im, c[mm][4]);
+                    }
+                }
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) gm_st4<T>(dgpred + (row * 3 + ch) * P + i, dg[ch]);
+                gm_st4<T>(dlpred + row * P + i, dl);
+                gm_st4<T>(dfpred + row * P + i, df);
+            }
+        }
+    } else {
+        for (size_t i = e0 + threadIdx.x; i < e1; i += 256) {
+            float a = 0.f, tv = 0.f, f[3] = {0.f, 0.f, 0.f}, bg[3] = {0.f, 0.f, 0.f}, im[3] = {0.f, 0.f, 0.f};
+            if (any) {
+                a = aa[i];
+                tv = tm[i];
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    f[ch] = ff[ch * P + i];
+                    bg[ch] = bb[ch * P + i];
+                    im[ch] = ii[ch * P + i];
+                }
+            }
+#pragma unroll
+            for (int mm = 0; mm < GM_M; ++mm) {
+                if (m0 + mm >= M) break;
+                const size_t row = (size_t)b * M + m0 + mm;
+                float d[3] = {0.f, 0.f, 0.f}, dl = 0.f, df = 0.f;
+                if (live[mm]) {
+                    const float gp[3] = {to_f32(gpred[row * 3 * P + i]), to_f32(gpred[(row * 3 + 1) * P + i]),
+                                         to_f32(gpred[(row * 3 + 2) * P + i])};
+                    const float lp = to_f32(lpred[row * P + i]), fp = to_f32(fpred[row * P + i]);
+                    tri_grad(gp, tv, 1e-4f, c[mm][0], c[mm][1], d);
+                    dl = alpha_grad(lp, a, tv == 128.f ? 1.f : 0.f, c[mm][2]);
+                    df = alpha_grad(fp, a, 1.f, c[mm][3]) + comp_px<1>(fp, f, bg, im, c[mm][4]);
+                }
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) dgpred[(row * 3 + ch) * P + i] = from_f32<T>(d[ch]);
+                dlpred[row * P + i] = from_f32<T>(dl);
+                dfpred[row * P + i] = from_f32<T>(df);
+            }
+        }
+    }
+}
+
 int mt_check(const char* what, int B, size_t P) {
     SAICV_REQUIRE(B > 0 && B <= 65535 && P > 0, "%s: 1 to 65535 samples of at least one pixel", what);
     SAICV_REQUIRE((P + MT_SPAN - 1) / MT_SPAN <= 0x7fffffffu, "%s: too many pixels per sample", what);
@@ -380,19 +603,20 @@ struct LapTable {
     float k[25];
 };
 
+// group: level 0 only -- row r of src reads alpha / trimap of sample r / group (1: a target row per source row)
 struct LapGeom {
-    int h, w, h2, w2, tiles_x, level0;
+    int h, w, h2, w2, tiles_x, level0, group;
 };
 
 DEVINL int lp_clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
-// the level's map at pixel `at` of the flat [B][h][w] arrays: level 0 forms (clamp(pred) - alpha) * w
+// the level's map at pixel `at` of the flat [B][h][w] array: level 0 forms (clamp(pred) - alpha) * w with the targets at `tat`
 DEVINL float lap_src(const float* __restrict__ src, const float* __restrict__ alpha, const float* __restrict__ trimap, size_t at,
-                     int level0) {
+                     size_t tat, int level0) {
     const float v = src[at];
     if (!level0) return v;
-    const float d = mt_clamp(v) - alpha[at];
-    return trimap ? (trimap[at] == 128.f ? d : 0.f * d) : d;
+    const float d = mt_clamp(v) - alpha[tat];
+    return trimap ? (trimap[tat] == 128.f ? d : 0.f * d) : d;
 }
 
 // G * cur for four neighbouring pixels from the five rows of eight values above and below them; the taps of one output are added
@@ -421,11 +645,11 @@ __global__ __launch_bounds__(256) void lap_fwd_kernel(const float* __restrict__ 
     __shared__ float F[LP_T][LP_T + 1];
     const int b = blockIdx.y, tile = blockIdx.x;
     const int ty0 = (tile / g.tiles_x) * LP_T, tx0 = (tile % g.tiles_x) * LP_T;
-    const size_t off = (size_t)b * g.h * g.w;
+    const size_t off = (size_t)b * g.h * g.w, toff = (size_t)(b / g.group) * g.h * g.w;
     for (int i = threadIdx.x; i < LP_IN * LP_IN; i += 256) {
         const int ly = i / LP_IN, lx = i - ly * LP_IN;
         const int y = lp_clampi(ty0 - 2 + ly, g.h - 1), x = lp_clampi(tx0 - 2 + lx, g.w - 1);
-        C[ly][lx] = lap_src(src, alpha, trimap, off + (size_t)y * g.w + x, g.level0);
+        C[ly][lx] = lap_src(src, alpha, trimap, off + (size_t)y * g.w + x, toff + (size_t)y * g.w + x, g.level0);
     }
     __syncthreads();
     const int r = threadIdx.x >> 3, c0 = (threadIdx.x & 7) * 4;
@@ -449,24 +673,39 @@ __global__ __launch_bounds__(256) void lap_fwd_kernel(const float* __restrict__ 
 
 // g_cur (level 0: dL/dpred) of the tile.  gnext: dL/dnext [B][h2][w2], or with topcur != null gtop[b] * sign(topcur) (the last
 // level: the sixth pyramid entry is next itself).  gs[b] = dL/d(sum |e|) of this level.
+// gall (or null) [nsum][B]: every dL/dsums of the pyramid.  A row b whose nsum entries are all zero takes no pass: level 0 writes
+// zeros without reading src, a coarser level writes nothing (the finer level of that row does not read it).
 __global__ __launch_bounds__(256) void lap_bwd_kernel(const float* __restrict__ src, const float* __restrict__ alpha,
                                                       const float* __restrict__ trimap, const float* __restrict__ gnext,
                                                       const float* __restrict__ topcur, const float* __restrict__ gs,
-                                                      const float* __restrict__ gtop, float* __restrict__ gcur, LapTable K,
-                                                      LapGeom g) {
+                                                      const float* __restrict__ gtop, const float* __restrict__ gall, int nsum,
+                                                      float* __restrict__ gcur, LapTable K, LapGeom g) {
     __shared__ float C[LP_BC][LP_BC + 1];
     __shared__ float GF[LP_IN][LP_IN + 1];
     __shared__ float SS[LP_IN][LP_IN + 1];
     __shared__ float Ks[25];
     const int b = blockIdx.y, tile = blockIdx.x;
     const int ty0 = (tile / g.tiles_x) * LP_T, tx0 = (tile % g.tiles_x) * LP_T;
-    const size_t off = (size_t)b * g.h * g.w;
+    const size_t off = (size_t)b * g.h * g.w, toff = (size_t)(b / g.group) * g.h * g.w;
+    if (gall != nullptr) {
+        bool any = false;
+        for (int j = 0; j < nsum; ++j) any = any || gall[(size_t)j * gridDim.y + b] != 0.f;
+        if (!any) {                                                     // uniform over the workgroup: no barrier is skipped by a part
+            if (g.level0) {
+                for (int i = threadIdx.x; i < LP_T * LP_T; i += 256) {
+                    const int y = ty0 + i / LP_T, x = tx0 + i % LP_T;
+                    if (y < g.h && x < g.w) gcur[off + (size_t)y * g.w + x] = 0.f;
+                }
+            }
+            return;
+        }
+    }
     const float gsv = gs[b];
     if (threadIdx.x < 25) Ks[threadIdx.x] = K.k[threadIdx.x];
     for (int i = threadIdx.x; i < LP_BC * LP_BC; i += 256) {
         const int ly = i / LP_BC, lx = i - ly * LP_BC;
         const int y = lp_clampi(ty0 - 4 + ly, g.h - 1), x = lp_clampi(tx0 - 4 + lx, g.w - 1);
-        C[ly][lx] = lap_src(src, alpha, trimap, off + (size_t)y * g.w + x, g.level0);
+        C[ly][lx] = lap_src(src, alpha, trimap, off + (size_t)y * g.w + x, toff + (size_t)y * g.w + x, g.level0);
     }
     __syncthreads();
     // gF = P^T g_next - gs sign(e) on the 36 x 36 ring, zero outside the image: 9 rows x 36 columns in groups of four
@@ -536,16 +775,17 @@ __global__ __launch_bounds__(256) void lap_bwd_kernel(const float* __restrict__ 
         const size_t at = off + (size_t)y * g.w + x;
         float v = SS[r + 2][c0 + j + 2] + out[j];
         if (g.level0) {
-            const bool on = mt_inside(src[at]) && (trimap == nullptr || trimap[at] == 128.f);
+            const bool on = mt_inside(src[at]) && (trimap == nullptr || trimap[toff + (size_t)y * g.w + x] == 128.f);
             v = on ? v : 0.f;
         }
         gcur[at] = v;
     }
 }
 
-int lap_geom(LapGeom& g, const char* what, int B, int h, int w, int level0) {
+int lap_geom(LapGeom& g, const char* what, int B, int h, int w, int level0, int group = 1) {
     SAICV_REQUIRE(B > 0 && B <= 65535 && h > 0 && w > 0, "%s: 1 to 65535 samples of at least one pixel", what);
-    g.h = h; g.w = w; g.h2 = h / 2; g.w2 = w / 2; g.level0 = level0 ? 1 : 0;
+    SAICV_REQUIRE(group >= 1 && B % group == 0, "%s: %d rows are no whole groups of %d", what, B, group);
+    g.h = h; g.w = w; g.h2 = h / 2; g.w2 = w / 2; g.level0 = level0 ? 1 : 0; g.group = group;
     g.tiles_x = (w + LP_T - 1) / LP_T;
     SAICV_REQUIRE((size_t)g.tiles_x * ((h + LP_T - 1) / LP_T) <= 0x7fffffffu, "%s: more than 2^31 - 1 tiles", what);
     return 0;
@@ -643,6 +883,60 @@ int matting_fuse_bwd(const float* gp, long sb, long sc, long sp, const float* df
     return check_launch("matting_fuse_bwd");
 }
 
+size_t group_matting_ws_floats(int B, int M, size_t P) {
+    if (B <= 0 || M <= 0 || P == 0) return 0;
+    return (size_t)B * ((M + GM_M - 1) / GM_M) * ((P + MT_SPAN - 1) / MT_SPAN) * (GM_M * GM_K);
+}
+
+namespace {
+int gm_check(const char* what, int dtype, const void* gp, const void* lp, const void* fp, const float* alpha, const float* trimap,
+             const float* image, const float* fg, const float* bg, int B, int M, size_t P) {
+    if (mt_check(what, B, P)) return -1;
+    SAICV_REQUIRE(dtype == SAICV_DTYPE_BF16 || dtype == SAICV_DTYPE_F32, "%s: predictions are bf16 or fp32", what);
+    SAICV_REQUIRE(M > 0 && (M + GM_M - 1) / GM_M <= 65535, "%s: 1 to %d masks per sample", what, 65535 * GM_M);
+    SAICV_REQUIRE(gp && lp && fp && alpha && trimap && image && fg && bg, "%s: null argument", what);
+    return 0;
+}
+}  // namespace
+
+int group_matting_stats_fwd(int dtype, const void* gp, const void* lp, const void* fp, const float* alpha, const float* trimap,
+                            const float* image, const float* fg, const float* bg, int B, int M, size_t P, float thr, float* partial,
+                            float* stats, hipStream_t st) {
+    if (gm_check("group_matting_stats_fwd", dtype, gp, lp, fp, alpha, trimap, image, fg, bg, B, M, P)) return -1;
+    SAICV_REQUIRE(partial != nullptr && stats != nullptr, "group_matting_stats_fwd: null workspace or output");
+    const GmTargets t = {alpha, trimap, image, fg, bg};
+    const int vec = P % 4 == 0 && mt_al16(gp) && mt_al16(lp) && mt_al16(fp) && mt_al16(alpha) && mt_al16(trimap) && mt_al16(image) &&
+                    mt_al16(fg) && mt_al16(bg);
+    const int nblk = mt_nblk(P), groups = (M + GM_M - 1) / GM_M;
+    const dim3 grid(nblk, B, groups);
+    if (dtype == SAICV_DTYPE_BF16)
+        hipLaunchKernelGGL(group_stats_fwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)gp, (const bf16_t*)lp,
+                           (const bf16_t*)fp, t, P, M, vec, thr, partial);
+    else
+        hipLaunchKernelGGL(group_stats_fwd_kernel<float>, grid, dim3(256), 0, st, (const float*)gp, (const float*)lp,
+                           (const float*)fp, t, P, M, vec, thr, partial);
+    hipLaunchKernelGGL(group_stats_fold_kernel, dim3(B * groups), dim3(256), 0, st, partial, nblk, M, groups, stats);
+    return check_launch("group_matting_stats_fwd");
+}
+
+int group_matting_stats_bwd(int dtype, const void* gp, const void* lp, const void* fp, const float* alpha, const float* trimap,
+                            const float* image, const float* fg, const float* bg, const float* gstats, int B, int M, size_t P,
+                            void* dgp, void* dlp, void* dfp, hipStream_t st) {
+    if (gm_check("group_matting_stats_bwd", dtype, gp, lp, fp, alpha, trimap, image, fg, bg, B, M, P)) return -1;
+    SAICV_REQUIRE(gstats && dgp && dlp && dfp, "group_matting_stats_bwd: null gradient");
+    const GmTargets t = {alpha, trimap, image, fg, bg};
+    const int vec = P % 4 == 0 && mt_al16(gp) && mt_al16(lp) && mt_al16(fp) && mt_al16(alpha) && mt_al16(trimap) && mt_al16(image) &&
+                    mt_al16(fg) && mt_al16(bg) && mt_al16(dgp) && mt_al16(dlp) && mt_al16(dfp);
+    const dim3 grid(mt_nblk(P), B, (M + GM_M - 1) / GM_M);
+    if (dtype == SAICV_DTYPE_BF16)
+        hipLaunchKernelGGL(group_stats_bwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)gp, (const bf16_t*)lp,
+                           (const bf16_t*)fp, t, gstats, P, M, vec, (bf16_t*)dgp, (bf16_t*)dlp, (bf16_t*)dfp);
+    else
+        hipLaunchKernelGGL(group_stats_bwd_kernel<float>, grid, dim3(256), 0, st, (const float*)gp, (const float*)lp,
+                           (const float*)fp, t, gstats, P, M, vec, (float*)dgp, (float*)dlp, (float*)dfp);
+    return check_launch("group_matting_stats_bwd");
+}
+
 size_t lap_level_ws_floats(int B, int h, int w) {
     if (B <= 0 || h <= 0 || w <= 0) return 0;
     return (size_t)B * ((h + LP_T - 1) / LP_T) * ((w + LP_T - 1) / LP_T) * 2;
@@ -677,8 +971,38 @@ int lap_level_bwd(const float* src, const float* alpha, const float* trimap, int
     LapTable K;
     for (int i = 0; i < 25; ++i) K.k[i] = table[i];
     hipLaunchKernelGGL(lap_bwd_kernel, dim3(lap_tiles(g), B), dim3(256), 0, st, src, level0 ? alpha : nullptr,
-                       level0 ? trimap : nullptr, gnext, topcur, gs, gtop, gcur, K, g);
+                       level0 ? trimap : nullptr, gnext, topcur, gs, gtop, (const float*)nullptr, 0, gcur, K, g);
     return check_launch("lap_level_bwd");
+}
+
+int lap_level0_group_fwd(const float* src, const float* alpha, const float* trimap, int group, int R, int h, int w, const float* table,
+                         float* next, float* partial, float* sum_e, hipStream_t st) {
+    LapGeom g;
+    if (lap_geom(g, "lap_level0_group_fwd", R, h, w, 1, group)) return -1;
+    SAICV_REQUIRE(src && alpha && table && partial && sum_e, "lap_level0_group_fwd: null argument");
+    SAICV_REQUIRE(next != nullptr || g.h2 == 0 || g.w2 == 0, "lap_level0_group_fwd: null output map");
+    LapTable K;
+    for (int i = 0; i < 25; ++i) K.k[i] = table[i];
+    const int tiles = lap_tiles(g);
+    hipLaunchKernelGGL(lap_fwd_kernel, dim3(tiles, R), dim3(256), 0, st, src, alpha, trimap, next, partial, K, g);
+    hipLaunchKernelGGL((mt_fold_kernel<2, 1>), dim3(R), dim3(256), 0, st, partial, tiles, sum_e, 1L, 0L);
+    return check_launch("lap_level0_group_fwd");
+}
+
+int lap_level_group_bwd(const float* src, const float* alpha, const float* trimap, int level0, int group, int R, int h, int w,
+                        const float* table, const float* gnext, const float* topcur, const float* gs, const float* gtop,
+                        const float* gall, int nsum, float* gcur, hipStream_t st) {
+    LapGeom g;
+    if (lap_geom(g, "lap_level_group_bwd", R, h, w, level0, level0 ? group : 1)) return -1;
+    SAICV_REQUIRE(src && table && gs && gall && gcur && nsum > 0, "lap_level_group_bwd: null argument");
+    SAICV_REQUIRE(!level0 || alpha != nullptr, "lap_level_group_bwd: level 0 needs alpha");
+    SAICV_REQUIRE(g.h2 == 0 || g.w2 == 0 || gnext != nullptr || (topcur != nullptr && gtop != nullptr),
+                  "lap_level_group_bwd: neither the next level's gradient nor the top map");
+    LapTable K;
+    for (int i = 0; i < 25; ++i) K.k[i] = table[i];
+    hipLaunchKernelGGL(lap_bwd_kernel, dim3(lap_tiles(g), R), dim3(256), 0, st, src, level0 ? alpha : nullptr,
+                       level0 ? trimap : nullptr, gnext, topcur, gs, gtop, gall, nsum, gcur, K, g);
+    return check_launch("lap_level_group_bwd");
 }
 
 }  // namespace saicv

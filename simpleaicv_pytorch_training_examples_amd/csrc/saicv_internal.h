@@ -148,6 +148,19 @@ int lap_level_fwd(const float* src, const float* alpha, const float* trimap, int
                   float* next, float* partial, float* sum_e, float* sum_next, hipStream_t st);
 int lap_level_bwd(const float* src, const float* alpha, const float* trimap, int level0, int B, int h, int w, const float* table,
                   const float* gnext, const float* topcur, const float* gs, const float* gtop, float* gcur, hipStream_t st);
+// grouped forms (SAM matting): prediction rows (b, m), targets rows b; stats / gstats [B][M][8]
+size_t group_matting_ws_floats(int B, int M, size_t P);
+int group_matting_stats_fwd(int dtype, const void* gp, const void* lp, const void* fp, const float* alpha, const float* trimap,
+                            const float* image, const float* fg, const float* bg, int B, int M, size_t P, float thr, float* partial,
+                            float* stats, hipStream_t st);
+int group_matting_stats_bwd(int dtype, const void* gp, const void* lp, const void* fp, const float* alpha, const float* trimap,
+                            const float* image, const float* fg, const float* bg, const float* gstats, int B, int M, size_t P,
+                            void* dgp, void* dlp, void* dfp, hipStream_t st);
+int lap_level0_group_fwd(const float* src, const float* alpha, const float* trimap, int group, int R, int h, int w, const float* table,
+                         float* next, float* partial, float* sum_e, hipStream_t st);
+int lap_level_group_bwd(const float* src, const float* alpha, const float* trimap, int level0, int group, int R, int h, int w,
+                        const float* table, const float* gnext, const float* topcur, const float* gs, const float* gtop,
+                        const float* gall, int nsum, float* gcur, hipStream_t st);
 // parsing.hip: form = 0 (by class count), 1 (lane per row, C <= 32), 2 (wavefront per row)
 size_t pixel_class_terms_ws_floats(size_t rows);
 int pixel_class_terms_lane_max_classes();

@@ -2646,6 +2646,148 @@ def collaborative_matting(global_pred, local_pred):
     return MattingFuseFn.apply(global_pred, local)
 
 
+# ------------------------------------------------------------------------------ SAM matting: grouped forms (csrc/matting.hip)
+GROUP_MATTING_STATS = ('bce', 'iou', 'local_alpha', 'local_weight', 'fused_alpha', 'composition', 'intersection', 'union')
+
+
+class GroupMattingStatsFn(torch.autograd.Function):
+    """The raw sums of SAMMattingLoss (SimpleAICV/interactive_segmentation/losses_matting.py) for the M predictions of every sample
+    against that sample's ONE set of targets: a target value is loaded once per pixel and serves all M masks; the backward writes
+    every gradient element once and spends no read on a (b, m) row whose coefficients are all zero."""
+
+    @staticmethod
+    def forward(ctx, gp, lp, fp, alpha, trimap, image, fg, bg, thr):
+        b, m = gp.shape[0], gp.shape[1]
+        p = gp.shape[3] * gp.shape[4]
+        L, dev = lib(), gp.device
+        stats = torch.empty((b, m, len(GROUP_MATTING_STATS)), dtype=torch.float32, device=dev)
+        partial = torch.empty(L.saicv_group_matting_ws_floats(b, m, p), dtype=torch.float32, device=dev)
+        es = gp.element_size()
+        t0 = KernelTimer.begin('group_matting_stats')
+        check(L.saicv_group_matting_stats_fwd(dtype_code(gp.dtype), ptr(gp), ptr(lp), ptr(fp), ptr(alpha), ptr(trimap), ptr(image),
+                                              ptr(fg), ptr(bg), b, m, p, float(thr), ptr(partial), ptr(stats), stream()),
+              'group_matting_stats_fwd')
+        KernelTimer.end(t0, 'group_matting_stats', 0, (44 + 5 * es * m) * b * p)
+        ctx.save_for_backward(gp, lp, fp, alpha, trimap, image, fg, bg)
+        return stats
+
+    @staticmethod
+    def backward(ctx, g):
+        gp, lp, fp, alpha, trimap, image, fg, bg = ctx.saved_tensors
+        b, m = gp.shape[0], gp.shape[1]
+        p = gp.shape[3] * gp.shape[4]
+        g = g.float().contiguous()
+        dgp, dlp, dfp = torch.empty_like(gp), torch.empty_like(lp), torch.empty_like(fp)
+        es = gp.element_size()
+        t0 = KernelTimer.begin('group_matting_stats')
+        check(lib().saicv_group_matting_stats_bwd(dtype_code(gp.dtype), ptr(gp), ptr(lp), ptr(fp), ptr(alpha), ptr(trimap),
+                                                  ptr(image), ptr(fg), ptr(bg), ptr(g), b, m, p, ptr(dgp), ptr(dlp), ptr(dfp),
+                                                  stream()), 'group_matting_stats_bwd')
+        KernelTimer.end(t0, 'group_matting_stats', 0, (44 + 10 * es * m) * b * p)
+        return dgp, dlp, dfp, None, None, None, None, None, None
+
+
+def group_matting_stats(global_preds, local_preds, fused_preds, alpha, trimap, image, fg, bg, mask_threshold=0.5):
+    """global_preds [B, M, 3, H, W], local_preds and fused_preds [B, M, 1, H, W] probabilities (fp32 or bf16, one dtype; clamped to
+    [1e-4, 1 - 1e-4] in fp32 inside); alpha [B, 1, H, W], trimap [B, H, W], image, fg, bg [B, 3, H, W] -> fp32 [B, M, 8], the columns
+    GROUP_MATTING_STATS: sum of the 3-channel bce against the one-hot trimap class, sum of the per-pixel IoU term (smooth 1e-4),
+    sum sqrt(((local - alpha) w)^2 + 1e-12) and sum w (w = [trimap == 128]), sum sqrt((fused - alpha)^2 + 1e-12), the three-channel
+    composition sum, and the counts of [fused > thr & alpha > thr] and of their union (whole numbers; no gradient, as sum w)."""
+    require_gpu(global_preds, local_preds, fused_preds, alpha, trimap, image, fg, bg)
+    if global_preds.dim() != 5 or global_preds.shape[2] != 3:
+        raise ValueError(f'group_matting_stats: global_preds must be [B, M, 3, H, W], got {tuple(global_preds.shape)}')
+    b, m, _, h, w = global_preds.shape
+    dt = global_preds.dtype if global_preds.dtype in (torch.float32, torch.bfloat16) else torch.float32
+    if local_preds.dtype != dt or fused_preds.dtype != dt:
+        dt = torch.float32
+    preds = []
+    for name, t, c in (('global_preds', global_preds, 3), ('local_preds', local_preds, 1), ('fused_preds', fused_preds, 1)):
+        if tuple(t.shape) != (b, m, c, h, w):
+            raise ValueError(f'group_matting_stats: {name} must be [{b}, {m}, {c}, {h}, {w}], got {tuple(t.shape)}')
+        preds.append(t.to(dt).contiguous())
+    targets = []
+    for name, t, c in (('alpha', alpha, 1), ('trimap', trimap, 1), ('image', image, 3), ('fg', fg, 3), ('bg', bg, 3)):
+        if t.shape[0] != b or t.numel() != b * c * h * w:
+            raise ValueError(f'group_matting_stats: {name} must hold [{b}, {c}, {h}, {w}] values, got {tuple(t.shape)}')
+        targets.append(_f32c(t))
+    return GroupMattingStatsFn.apply(*preds, *targets, float(mask_threshold))
+
+
+class GroupLaplacianL1Fn(torch.autograd.Function):
+    """LaplacianL1Fn for pred [B * M, h, w] against alpha / trimap [B, h, w]: only level 0 reads the targets, so the group is a
+    parameter of that launch; the backward skips the pyramid pass of every row whose six coefficients are zero."""
+
+    @staticmethod
+    def forward(ctx, pred, alpha, trimap, table, group):
+        r, h, w = pred.shape
+        L, dev = lib(), pred.device
+        tab = (ctypes.c_float * 25)(*table)
+        sums = torch.empty((LAP_LEVELS + 1, r), dtype=torch.float32, device=dev)
+        levels, cur = [], pred
+        t0 = KernelTimer.begin('lap_level')
+        for l in range(LAP_LEVELS):
+            hl, wl = h >> l, w >> l
+            nxt = torch.empty((r, hl // 2, wl // 2), dtype=torch.float32, device=dev)
+            partial = torch.empty(L.saicv_lap_level_ws_floats(r, hl, wl), dtype=torch.float32, device=dev)
+            top = l == LAP_LEVELS - 1
+            if l == 0:
+                check(L.saicv_lap_level0_group_fwd(ptr(cur), ptr(alpha), ptr(trimap), group, r, hl, wl, tab, ptr(nxt), ptr(partial),
+                                                   sums.data_ptr(), stream()), 'lap_level0_group_fwd')
+            else:
+                check(L.saicv_lap_level_fwd(ptr(cur), 0, 0, 0, r, hl, wl, tab, ptr(nxt), ptr(partial), sums.data_ptr() + 4 * r * l,
+                                            sums.data_ptr() + 4 * r * LAP_LEVELS if top else 0, stream()), 'lap_level_fwd')
+            levels.append(nxt)
+            cur = nxt
+        KernelTimer.end(t0, 'lap_level', 50.0 * r * h * w * 4 / 3, 4 * r * h * w + (4 if trimap is None else 8) * r // group * h * w
+                        + 5 * r * h * w // 3 * 2)
+        ctx.save_for_backward(pred, alpha, trimap, *levels)
+        ctx.table, ctx.group = tuple(table), group
+        return sums
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, alpha, trimap, *levels = ctx.saved_tensors
+        r, h, w = pred.shape
+        L, dev = lib(), pred.device
+        tab = (ctypes.c_float * 25)(*ctx.table)
+        g = g.float().contiguous()
+        maps = [pred] + list(levels)
+        gnext = None
+        t0 = KernelTimer.begin('lap_level')
+        for l in range(LAP_LEVELS - 1, -1, -1):
+            hl, wl = h >> l, w >> l
+            top = l == LAP_LEVELS - 1
+            gcur = torch.empty((r, hl, wl), dtype=torch.float32, device=dev)
+            check(L.saicv_lap_level_group_bwd(ptr(maps[l]), ptr(alpha) if l == 0 else 0, ptr(trimap) if l == 0 else 0, int(l == 0),
+                                              ctx.group, r, hl, wl, tab, ptr(gnext), ptr(maps[l + 1]) if top else 0,
+                                              g.data_ptr() + 4 * r * l, g.data_ptr() + 4 * r * LAP_LEVELS if top else 0, ptr(g),
+                                              LAP_LEVELS + 1, ptr(gcur), stream()), 'lap_level_group_bwd')
+            gnext = gcur
+        KernelTimer.end(t0, 'lap_level', 0, 4 * r * h * w)
+        return gnext, None, None, None, None
+
+
+def group_laplacian_sums(pred, alpha, trimap=None, weights=None):
+    """laplacian_sums with M predictions per sample: pred [B, M, H, W] (or [B, M, 1, H, W]), alpha and trimap [B, H, W] (alpha also
+    [B, 1, H, W]) -> sums [6, B * M] fp32, row b * M + m.  No expanded copy of a target is made."""
+    pred2, alpha2, trimap2 = (None if t is None else _f32c(t) for t in (pred, alpha, trimap))
+    require_gpu(pred2, alpha2, trimap2)
+    if pred2.dim() == 5 and pred2.shape[2] == 1:
+        pred2 = pred2.view(pred2.shape[0], pred2.shape[1], pred2.shape[3], pred2.shape[4])
+    if pred2.dim() != 4:
+        raise ValueError(f'group_laplacian_sums: pred must be [B, M, H, W] or [B, M, 1, H, W], got {tuple(pred.shape)}')
+    b, m, h, w = pred2.shape
+    if min(h, w) < LAP_MIN_SIDE:
+        raise ValueError(f'group_laplacian_sums: a {h} x {w} map has no five pyramid levels; both sides must be at least '
+                         f'{LAP_MIN_SIDE}')
+    if alpha2.numel() != b * h * w or alpha2.shape[0] != b or (trimap2 is not None and tuple(trimap2.shape) != (b, h, w)):
+        raise ValueError(f'group_laplacian_sums: alpha / trimap must be [{b}, {h}, {w}]')
+    table = laplacian_gauss_table() if weights is None else tuple(float(v) for v in torch.as_tensor(weights).reshape(-1).tolist())
+    if len(table) != 25:
+        raise ValueError('group_laplacian_sums: the weight table holds 25 values (5 x 5, row-major)')
+    return GroupLaplacianL1Fn.apply(pred2.view(b * m, h, w), alpha2.view(b, h, w), trimap2, table, m)
+
+
 # ------------------------------------------------------------------------------ Muon: grouped Newton-Schulz (csrc/muon.hip)
 MUON_TILE = 64
 MUON_TAB = 13           # int32 per problem, the layout of csrc/muon.hip
