@@ -660,6 +660,29 @@ int saicv_ctc_loss_bwd(int dtype, const void* logits, long long st, long long sb
 int saicv_ctc_greedy(int dtype, const void* logits, long long st, long long sb, const int* input_lengths, int T, int B, int C,
                      int* index, float* prob, void* stream);
 
+/* ---- the set loss of universal segmentation (universal_segmentation/segmentation_losses.py: Mask2FormerHungarianMatcher and
+ * UniversalSegmentationLoss; csrc/univseg.hip).  mask_preds [B][Q][P] contiguous in dtype (bf16 or fp32), P = H * W of any size;
+ * targets [total_t][P] fp32, the masks of the whole batch packed image after image, values in [0, 1]; offsets [B + 1] int32 in
+ * device memory, image i owning rows offsets[i] .. offsets[i + 1) (an image may own none); max_t = the largest count.
+ * sums (3 * Q * total_t + B * Q + total_t floats) = three planes [Q][total_t] -- P = sum softplus(-x) y, N = sum softplus(x)(1 - y),
+ * S = sum sigmoid(x) y, column offsets[i] + t paired with the queries of image i only -- then sum sigmoid(x) [B][Q], then sum y
+ * [total_t].  fp32-operand MFMA products, fp32 accumulation, pixel chunks of saicv_univseg_chunk() added in chunk order: no atomics,
+ * the bits of an image's sums depend on (Q, T_i, P) alone.  partial: saicv_univseg_pair_ws_floats floats. */
+int saicv_univseg_chunk(void);
+size_t saicv_univseg_pair_ws_floats(int B, int Q, int total_t, size_t P);
+int saicv_univseg_pair_sums(int dtype, const void* mask_preds, const float* targets, const int* offsets, int B, int Q, int total_t,
+                            int max_t, size_t P, float* partial, float* sums, void* stream);
+/* Matched pairs m < M: pred_rows[m] = b * Q + q, target_rows[m] = offsets[b] + t (int32, device).  stats [M][4] = (sum
+ * BCEWithLogits(x, y), sum sigmoid(x) y, sum sigmoid(x), sum y); rows are read through the tables, no gather copy.
+ * partial: saicv_univseg_matched_ws_floats floats. */
+size_t saicv_univseg_matched_ws_floats(int M, size_t P);
+int saicv_univseg_matched_fwd(int dtype, const void* mask_preds, const float* targets, const int* pred_rows, const int* target_rows,
+                              int M, size_t P, float* partial, float* stats, void* stream);
+/* row_pair [rows = B * Q] int32: the pair of that prediction row or -1.  dmask_preds [rows][P] in dtype is written whole: a matched
+ * row g0 (s - y) + s (1 - s)(g1 y + g2) with g = gstats[m], s = sigmoid(x); every other row exact zeros. */
+int saicv_univseg_matched_bwd(int dtype, const void* mask_preds, const float* targets, const int* row_pair, const int* target_rows,
+                              const float* gstats, int rows, size_t P, void* dmask_preds, void* stream);
+
 /* One bidirectional LSTM layer's recurrence (nn.LSTM: one layer, batch_first, zero initial state, gate order i, f, g, o; csrc/lstm.hip).
  * The input projection and every parameter / input gradient are GEMMs on the entry points above; these two walk T.  H a multiple of
  * 32 in 32 .. 1024, any B >= 1 and T >= 1; both directions in one launch, no atomics, nothing read back.

@@ -273,6 +273,12 @@ SIGNATURES = {
     'saicv_ctc_loss_bwd': (c_int, [c_int, _P, ctypes.c_longlong, ctypes.c_longlong, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P,
                                    _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P]),
     'saicv_ctc_greedy': (c_int, [c_int, _P, ctypes.c_longlong, ctypes.c_longlong, _P, c_int, c_int, c_int, _P, _P, _P]),
+    'saicv_univseg_chunk': (c_int, []),
+    'saicv_univseg_pair_ws_floats': (c_size_t, [c_int, c_int, c_int, c_size_t]),
+    'saicv_univseg_pair_sums': (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_size_t, _P, _P, _P]),
+    'saicv_univseg_matched_ws_floats': (c_size_t, [c_int, c_size_t]),
+    'saicv_univseg_matched_fwd': (c_int, [c_int, _P, _P, _P, _P, c_int, c_size_t, _P, _P, _P]),
+    'saicv_univseg_matched_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_size_t, _P, _P]),
     'saicv_lstm_fwd': (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     'saicv_lstm_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     'saicv_attention_stream_fwd': (c_int, [c_int, c_int, _PA, _P]),

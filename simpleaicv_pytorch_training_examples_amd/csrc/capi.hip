@@ -721,6 +721,21 @@ int saicv_ctc_greedy(int dtype, const void* logits, long long st, long long sb, 
                      int* index, float* prob, void* stream) {
     return ctc_greedy(dtype, logits, st, sb, input_lengths, T, B, C, index, prob, S(stream));
 }
+int saicv_univseg_chunk(void) { return univseg_chunk(); }
+size_t saicv_univseg_pair_ws_floats(int B, int Q, int total_t, size_t P) { return univseg_pair_ws_floats(B, Q, total_t, P); }
+int saicv_univseg_pair_sums(int dtype, const void* mask_preds, const float* targets, const int* offsets, int B, int Q, int total_t,
+                            int max_t, size_t P, float* partial, float* sums, void* stream) {
+    return univseg_pair_sums(dtype, mask_preds, targets, offsets, B, Q, total_t, max_t, P, partial, sums, S(stream));
+}
+size_t saicv_univseg_matched_ws_floats(int M, size_t P) { return univseg_matched_ws_floats(M, P); }
+int saicv_univseg_matched_fwd(int dtype, const void* mask_preds, const float* targets, const int* pred_rows, const int* target_rows,
+                              int M, size_t P, float* partial, float* stats, void* stream) {
+    return univseg_matched_fwd(dtype, mask_preds, targets, pred_rows, target_rows, M, P, partial, stats, S(stream));
+}
+int saicv_univseg_matched_bwd(int dtype, const void* mask_preds, const float* targets, const int* row_pair, const int* target_rows,
+                              const float* gstats, int rows, size_t P, void* dmask_preds, void* stream) {
+    return univseg_matched_bwd(dtype, mask_preds, targets, row_pair, target_rows, gstats, rows, P, dmask_preds, S(stream));
+}
 int saicv_attention_stream_fwd(int dtype, int D, const saicv_attn_desc* desc, void* stream) {
     if (!desc) { set_error("attention_stream: null descriptor"); return -1; }
     return attention_stream(dtype, D, 0, desc, S(stream));

@@ -182,6 +182,17 @@ int ctc_loss_bwd(int dtype, const void* logits, long long st, long long sb, void
                  int focal, float gamma, hipStream_t s);
 int ctc_greedy(int dtype, const void* logits, long long st, long long sb, const int* in_len, int T, int B, int C, int* index,
                float* prob, hipStream_t s);
+// univseg.hip: the set loss of universal segmentation.  preds [B][Q][P] in dtype, targets [TT][P] fp32 packed over the batch,
+// offsets [B + 1] int32 (device); sums = 3 planes [Q][TT] (P, N, S; column offsets[i] + t), then qsum [B][Q], then tsum [TT]
+int univseg_chunk();
+size_t univseg_pair_ws_floats(int B, int Q, int TT, size_t P);
+int univseg_pair_sums(int dtype, const void* preds, const float* targets, const int* offsets, int B, int Q, int TT, int Tmax, size_t P,
+                      float* partial, float* sums, hipStream_t st);
+size_t univseg_matched_ws_floats(int M, size_t P);
+int univseg_matched_fwd(int dtype, const void* preds, const float* targets, const int* rowx, const int* rowy, int M, size_t P,
+                        float* partial, float* stats, hipStream_t st);
+int univseg_matched_bwd(int dtype, const void* preds, const float* targets, const int* rowmap, const int* rowy, const float* gstats,
+                        int R, size_t P, void* dpreds, hipStream_t st);
 // attn_stream.hip: which = 0 forward, 1 dQ pass, 2 dK/dV pass; desc = const saicv_attn_desc*
 int attention_stream(int dtype, int D, int which, const void* desc, hipStream_t st);
 

@@ -2863,3 +2863,136 @@ def muon_newton_schulz(tensors, steps=5, coeffs=MUON_COEFFS, normalize=True):
         u = plan.operand(k, buf)
         out.append((u.t() if plan.items[k][5] else u).contiguous())
     return out
+
+
+# ------------------------------------------------------------------------------ universal segmentation set loss (csrc/univseg.hip)
+MATCHED_MASK_STATS = ('bce', 'intersection', 'pred_sum', 'target_sum')
+
+
+def mask_pair_chunk():
+    """Pixels per workgroup of the pair-sum and matched-statistics kernels: H * W is split into chunks of this length whose
+    partial sums are added in chunk order."""
+    return int(lib().saicv_univseg_chunk())
+
+
+def _mask_offsets(offsets, b):
+    host = [int(v) for v in (offsets.tolist() if torch.is_tensor(offsets) else offsets)]
+    if len(host) != b + 1 or host[0] != 0 or any(host[i + 1] < host[i] for i in range(b)):
+        raise ValueError(f'offsets must be a non-decreasing table of {b + 1} entries starting at 0, got {host}')
+    return host
+
+
+def _mask_operands(mask_preds, targets, total):
+    require_gpu(mask_preds, targets)
+    if mask_preds.dim() != 4:
+        raise ValueError(f'mask_preds must be [B, Q, H, W], got {tuple(mask_preds.shape)}')
+    b, q, h, w = mask_preds.shape
+    if mask_preds.dtype not in (torch.float32, torch.bfloat16):
+        mask_preds = mask_preds.float()
+    mask_preds = mask_preds.contiguous()
+    targets = _f32c(targets)
+    if tuple(targets.shape) != (total, h, w):
+        raise ValueError(f'targets must be the packed [{total}, {h}, {w}] masks of the batch, got {tuple(targets.shape)}')
+    return mask_preds, targets
+
+
+def mask_pair_sums(mask_preds, targets, offsets):
+    """mask_preds [B, Q, H, W] logits (bf16 or fp32), targets [sum T_i, H, W] in [0, 1] packed image after image, offsets the B + 1
+    row bounds (a list or an int tensor; T_i = 0 is legal) -> (pos, neg, inter, pred_sum, target_sum), fp32:
+    pos / neg / inter [Q, sum T_i] = sum_p softplus(-x) y, sum_p softplus(x)(1 - y), sum_p sigmoid(x) y, column offsets[i] + t
+    paired with the queries of image i; pred_sum [B, Q] = sum_p sigmoid(x); target_sum [sum T_i] = sum_p y.  Ordered sums: the
+    bits of an image's values depend on its own shapes alone, in every mode."""
+    b = mask_preds.shape[0]
+    host = _mask_offsets(offsets, b)
+    total = host[-1]
+    mask_preds, targets = _mask_operands(mask_preds, targets, total)
+    q, p = mask_preds.shape[1], mask_preds.shape[2] * mask_preds.shape[3]
+    L, dev = lib(), mask_preds.device
+    off = torch.tensor(host, dtype=torch.int32).to(dev, non_blocking=True)
+    sums = torch.empty(3 * q * total + b * q + total, dtype=torch.float32, device=dev)
+    partial = torch.empty(L.saicv_univseg_pair_ws_floats(b, q, total, p), dtype=torch.float32, device=dev)
+    tmax = max(host[i + 1] - host[i] for i in range(b))
+    t0 = KernelTimer.begin('univseg_pair_sums')
+    check(L.saicv_univseg_pair_sums(dtype_code(mask_preds.dtype), ptr(mask_preds), ptr(targets), ptr(off), b, q, total, tmax, p,
+                                    ptr(partial), ptr(sums), stream()), 'univseg_pair_sums')
+    KernelTimer.end(t0, 'univseg_pair_sums', 6.0 * q * total * p, mask_preds.element_size() * b * q * p + 4 * total * p)
+    plane = q * total
+    return (sums[:plane].view(q, total), sums[plane:2 * plane].view(q, total), sums[2 * plane:3 * plane].view(q, total),
+            sums[3 * plane:3 * plane + b * q].view(b, q), sums[3 * plane + b * q:])
+
+
+def mask_match_cost(mask_preds, class_preds, targets, offsets, labels, mask_cost=1.0, dice_cost=1.0, class_cost=1.0):
+    """The cost matrices of Mask2FormerHungarianMatcher (universal_segmentation/segmentation_losses.py) for the whole batch, PACKED:
+    fp32 [Q, sum T_i] on the device, columns offsets[i] .. offsets[i + 1) being image i's [Q, T_i] matrix
+        mask_cost (P + N) / (H W) + dice_cost (1 - (2 S + 1) / (sum sigmoid + sum y + 1)) - class_cost softmax(class_preds)[q, label_t]
+    clamped to +-1e10 with NaN -> 0.  class_preds [B, Q, C], labels the packed [sum T_i] class ids.  One copy to the host then serves
+    every image's assignment."""
+    b, q = mask_preds.shape[0], mask_preds.shape[1]
+    host = _mask_offsets(offsets, b)
+    pos, neg, inter, pred_sum, target_sum = mask_pair_sums(mask_preds, targets, host)
+    dev = mask_preds.device
+    counts = torch.tensor([host[i + 1] - host[i] for i in range(b)], dtype=torch.int64)
+    image = torch.repeat_interleave(torch.arange(b, dtype=torch.int64), counts).to(dev, non_blocking=True)
+    labels = labels.to(device=dev, dtype=torch.int64)
+    hw = mask_preds.shape[2] * mask_preds.shape[3]
+    probs = class_preds.float().softmax(dim=-1)
+    cls = probs[image, :, labels].t()                                              # [Q, sum T]
+    dice = 1 - (2 * inter + 1) / (pred_sum[image].t() + target_sum[None, :] + 1)
+    cost = mask_cost * ((pos + neg) / hw) + dice_cost * dice - class_cost * cls
+    return torch.nan_to_num(cost.clamp(min=-1e10, max=1e10), 0)
+
+
+class MatchedMaskStatsFn(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, mask_preds, targets, rowx, rowy, rowmap):
+        m = rowx.numel()
+        p = mask_preds.shape[2] * mask_preds.shape[3]
+        L, dev = lib(), mask_preds.device
+        stats = torch.empty((m, 4), dtype=torch.float32, device=dev)
+        if m:
+            partial = torch.empty(L.saicv_univseg_matched_ws_floats(m, p), dtype=torch.float32, device=dev)
+            t0 = KernelTimer.begin('univseg_matched')
+            check(L.saicv_univseg_matched_fwd(dtype_code(mask_preds.dtype), ptr(mask_preds), ptr(targets), ptr(rowx), ptr(rowy), m, p,
+                                              ptr(partial), ptr(stats), stream()), 'univseg_matched_fwd')
+            KernelTimer.end(t0, 'univseg_matched', 0, (mask_preds.element_size() + 4) * m * p)
+        ctx.save_for_backward(mask_preds, targets, rowy, rowmap)
+        return stats
+
+    @staticmethod
+    def backward(ctx, g):
+        mask_preds, targets, rowy, rowmap = ctx.saved_tensors
+        b, q, h, w = mask_preds.shape
+        g = g.float().contiguous()
+        dpreds = torch.empty_like(mask_preds)
+        t0 = KernelTimer.begin('univseg_matched')
+        check(lib().saicv_univseg_matched_bwd(dtype_code(mask_preds.dtype), ptr(mask_preds), ptr(targets), ptr(rowmap), ptr(rowy),
+                                              ptr(g), b * q, h * w, ptr(dpreds), stream()), 'univseg_matched_bwd')
+        KernelTimer.end(t0, 'univseg_matched', 0, mask_preds.element_size() * (b * q + rowy.numel()) * h * w + 4 * rowy.numel() * h * w)
+        return dpreds, None, None, None, None
+
+
+def matched_mask_stats(mask_preds, targets, pair_b, pair_q, pair_t):
+    """The pixel sums of the matched pairs of UniversalSegmentationLoss: pair m joins row (pair_b[m], pair_q[m]) of mask_preds
+    [B, Q, H, W] (bf16 or fp32 logits) with row pair_t[m] of the packed targets [sum T_i, H, W] (pair_t indexes the PACKED rows:
+    offsets[b] + t) -> fp32 [M, 4], the columns MATCHED_MASK_STATS: sum BCEWithLogits(x, y), sum sigmoid(x) y, sum sigmoid(x), sum y.
+    Rows are read through the index tensors, no gather copy.  Differentiable in mask_preds: the backward writes the whole
+    [B, Q, H, W] gradient in mask_preds' dtype, exact zeros in every unmatched row.  A (b, q) that occurs twice raises."""
+    pb, pq, pt = (torch.as_tensor(t).reshape(-1).to('cpu', torch.int64) for t in (pair_b, pair_q, pair_t))
+    if not (pb.numel() == pq.numel() == pt.numel()):
+        raise ValueError('matched_mask_stats: pair_b, pair_q and pair_t must have one length')
+    total = targets.shape[0]
+    mask_preds, targets = _mask_operands(mask_preds, targets, total)
+    b, q = mask_preds.shape[0], mask_preds.shape[1]
+    m = pb.numel()
+    if m and (int(pb.min()) < 0 or int(pb.max()) >= b or int(pq.min()) < 0 or int(pq.max()) >= q or int(pt.min()) < 0
+              or int(pt.max()) >= total):
+        raise ValueError('matched_mask_stats: a pair index is out of range')
+    rows = pb * q + pq
+    if torch.unique(rows).numel() != m:
+        raise RuntimeError('matched_mask_stats: a (b, q) prediction row is matched twice; an assignment never does that')
+    rowmap = torch.full((b * q, ), -1, dtype=torch.int32)
+    rowmap[rows] = torch.arange(m, dtype=torch.int32)
+    dev = mask_preds.device
+    return MatchedMaskStatsFn.apply(mask_preds, targets, rows.to(torch.int32).to(dev, non_blocking=True),
+                                    pt.to(torch.int32).to(dev, non_blocking=True), rowmap.to(dev, non_blocking=True))
