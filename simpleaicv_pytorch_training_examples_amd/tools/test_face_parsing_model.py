@@ -11,15 +11,9 @@ and log lines as the reference tools/test_face_parsing_model.py:
 
 As in the reference the loaders are NOT sharded (every rank evaluates every set; rank 0 logs)."""
 import argparse
-import os
-import sys
 
-import torch
-from torch.utils.data import DataLoader
-
-from .. import engine
+from . import entry
 from .face_parsing_scripts import validate_face_parsing_for_all_dataset
-from .utils import compute_macs_and_params, get_logger, set_seed
 
 
 def parse_args():
@@ -28,48 +22,12 @@ def parse_args():
     return parser.parse_args()
 
 
+TASK = entry.TestTask(validate=validate_face_parsing_for_all_dataset, eval_loaders=entry.dataset_list_loaders,
+                      report=entry.report_datasets)
+
+
 def main():
-    assert torch.cuda.is_available(), 'need gpu to train network!'
-    args = parse_args()
-    sys.path.append(args.work_dir)
-    from test_config import config
-    log_dir = os.path.join(args.work_dir, 'log')
-    config.gpus_type = torch.cuda.get_device_name()
-    config.gpus_num = int(os.environ.get('WORLD_SIZE', torch.cuda.device_count()))
-    set_seed(config.seed)
-    local_rank = int(os.environ['LOCAL_RANK'])
-    config.local_rank = local_rank
-    torch.cuda.set_device(local_rank)
-    torch.distributed.init_process_group(backend='nccl', init_method='env://', device_id=torch.device('cuda', local_rank))
-    config.group = torch.distributed.new_group(list(range(config.gpus_num)))
-    os.makedirs(log_dir, exist_ok=True)
-    torch.distributed.barrier(device_ids=[local_rank])
-    logger = get_logger('test', log_dir)
-    info = (lambda m: logger.info(m)) if local_rank == 0 else (lambda m: None)
-
-    assert config.batch_size % config.gpus_num == 0, 'config.batch_size is not divisible by config.gpus_num!'
-    assert config.num_workers % config.gpus_num == 0, 'config.num_workers is not divisible by config.gpus_num!'
-    batch_size = int(config.batch_size // config.gpus_num)
-    num_workers = int(config.num_workers // config.gpus_num)
-    val_loader_list = [DataLoader(dataset, batch_size=batch_size, shuffle=False, pin_memory=True, num_workers=num_workers,
-                                  collate_fn=config.val_collater) for dataset in config.val_dataset_list]
-    for key, value in config.__dict__.items():
-        if not key.startswith('__') and key not in ['model']:
-            info(f'{key}: {value}')
-
-    model, test_criterion = config.model, config.test_criterion
-    flops, macs, params = compute_macs_and_params(config, model)
-    info(f'model: {config.network}, flops: {flops}, macs: {macs}, params: {params}')
-    model = model.cuda()
-    test_criterion = test_criterion.cuda()
-    model = engine.DistributedDataParallel(model, device_ids=[local_rank], output_device=local_rank, process_group=config.group)
-    result_dict = validate_face_parsing_for_all_dataset(val_loader_list, model, test_criterion, config)
-    for name, per_dataset in result_dict.items():
-        log_info = f'eval dataset:{name}\n'
-        for key, value in per_dataset.items():
-            log_info += f'{key}: {value}\n'
-        info(log_info)
-    torch.distributed.destroy_process_group()
+    entry.test(parse_args, TASK)
 
 
 if __name__ == '__main__':

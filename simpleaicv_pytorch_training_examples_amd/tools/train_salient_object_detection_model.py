@@ -14,17 +14,10 @@ Checkpoints: checkpoints/latest.pth = {epoch, time, best_metric, test_loss, lr, 
 best weights (unprefixed) -> best.pth -> `{network}-metric{best:.3f}.pth` at the end.
 """
 import argparse
-import functools
-import os
-import sys
-import time
 
-import torch
-from torch.utils.data import DataLoader
-
-from .salient_object_detection_scripts import (first_dataset_metric, train_salient_object_detection_segmentation,
-                                                validate_salient_object_detection_segmentation_for_all_dataset)
-from .utils import Scheduler, build_optimizer, build_training_mode, get_logger, set_seed, worker_seed_init_fn
+from . import entry
+from .salient_object_detection_scripts import (train_salient_object_detection_segmentation,
+                                               validate_salient_object_detection_segmentation_for_all_dataset)
 
 
 def parse_args():
@@ -33,130 +26,13 @@ def parse_args():
     return parser.parse_args()
 
 
+TASK = entry.TrainTask(train=train_salient_object_detection_segmentation, best=entry.BEST_METRIC, criterion_dict=True,
+                       eval_loaders=entry.dataset_list_loaders, validate=validate_salient_object_detection_segmentation_for_all_dataset,
+                       evaluate=entry.evaluate_first_dataset, epoch_weights=True)
+
+
 def main():
-    assert torch.cuda.is_available(), 'need gpu to train network!'
-    args = parse_args()
-    sys.path.append(args.work_dir)
-    from train_config import config
-    log_dir = os.path.join(args.work_dir, 'log')
-    checkpoint_dir = os.path.join(args.work_dir, 'checkpoints')
-    resume_model = os.path.join(checkpoint_dir, 'latest.pth')
-    config.gpus_type = torch.cuda.get_device_name()
-    config.gpus_num = int(os.environ.get('WORLD_SIZE', torch.cuda.device_count()))
-    set_seed(config.seed)
-    local_rank = int(os.environ['LOCAL_RANK'])
-    config.local_rank = local_rank
-    torch.cuda.set_device(local_rank)
-    torch.distributed.init_process_group(backend='nccl', init_method='env://',
-                                         device_id=torch.device('cuda', local_rank))
-    config.group = torch.distributed.new_group(list(range(config.gpus_num)))
-    os.makedirs(checkpoint_dir, exist_ok=True)
-    os.makedirs(log_dir, exist_ok=True)
-    torch.distributed.barrier(device_ids=[local_rank])
-    logger = get_logger('train', log_dir)
-    info = (lambda m: logger.info(m)) if local_rank == 0 else (lambda m: None)
-
-    assert config.batch_size % config.gpus_num == 0, 'config.batch_size is not divisible by config.gpus_num!'
-    assert config.num_workers % config.gpus_num == 0, 'config.num_workers is not divisible by config.gpus_num!'
-    batch_size = int(config.batch_size // config.gpus_num)
-    num_workers = int(config.num_workers // config.gpus_num)
-    init_fn = functools.partial(worker_seed_init_fn, num_workers=num_workers, local_rank=local_rank, seed=config.seed)
-    train_sampler = torch.utils.data.distributed.DistributedSampler(config.train_dataset, shuffle=True)
-    train_loader = DataLoader(config.train_dataset, batch_size=batch_size, shuffle=False, pin_memory=True,
-                              drop_last=True, num_workers=num_workers, collate_fn=config.train_collater,
-                              sampler=train_sampler, worker_init_fn=init_fn)
-    val_loader_list = [DataLoader(dataset, batch_size=batch_size, shuffle=False, pin_memory=True, num_workers=num_workers,
-                                  collate_fn=config.val_collater) for dataset in config.val_dataset_list]
-
-    for key, value in config.__dict__.items():
-        if not key.startswith('__') and key not in ['model']:
-            info(f'{key}: {value}')
-
-    model = config.model.cuda()
-    train_criterion = {name: loss.cuda() for name, loss in config.train_criterion.items()}
-    test_criterion = config.test_criterion.cuda()
-    info('--------------------parameters--------------------')
-    for name, param in model.named_parameters():
-        info(f'name: {name}, grad: {param.requires_grad}')
-    info('--------------------buffers--------------------')
-    for name, buffer in model.named_buffers():
-        info(f'name: {name}, grad: {buffer.requires_grad}')
-
-    optimizer, model_layer_weight_decay_list = build_optimizer(config, model)
-    info('-------------layers weight decay---------------')
-    for per_layer_list in model_layer_weight_decay_list:
-        lr_scale = per_layer_list.get('lr_scale', 'not setting!')
-        for name in per_layer_list['name']:
-            info(f"name: {name}, lr: {per_layer_list['lr']}, weight_decay: {per_layer_list['weight_decay']}, "
-                 f'lr_scale: {lr_scale}')
-
-    scheduler = Scheduler(config, optimizer)
-    model, config.ema_model, config.scaler = build_training_mode(config, model)
-
-    start_epoch, train_time = 1, 0
-    best_metric, metric, test_loss = 0, 0, 0
-    if os.path.exists(resume_model):
-        checkpoint = torch.load(resume_model, map_location=torch.device('cpu'), weights_only=True)
-        model.load_state_dict(checkpoint['model_state_dict'])
-        optimizer.load_state_dict(checkpoint['optimizer_state_dict'])
-        scheduler.load_state_dict(checkpoint['scheduler_state_dict'])
-        saved_epoch = checkpoint['epoch']
-        start_epoch += saved_epoch
-        used_time = checkpoint['time']
-        train_time += used_time
-        best_metric, test_loss, lr = checkpoint['best_metric'], checkpoint['test_loss'], checkpoint['lr']
-        info(f'resuming model from {resume_model}. resume_epoch: {saved_epoch:0>3d}, used_time: {used_time:.3f} hours, '
-             f'best_metric: {best_metric:.3f}, test_loss: {test_loss}, lr: {lr:.6f}')
-        if 'ema_model_state_dict' in checkpoint.keys():
-            config.ema_model.ema_model.load_state_dict(checkpoint['ema_model_state_dict'])
-        from .. import ops
-        ops.bump_weights_epoch()
-
-    info(f'using torch version:{torch.__version__}')
-    # torch.compile (Inductor -> Triton) is not part of the MI355X-native path; the fused HIP
-    # kernels and the launch graph replace it.  `use_compile` is accepted and ignored.
-    config.compile_support = False
-    config.use_compile = False
-
-    for epoch in range(start_epoch, config.epochs + 1):
-        per_epoch_start_time = time.time()
-        info(f'epoch {epoch:0>3d} lr: {scheduler.current_lr:.6f}')
-        train_sampler.set_epoch(epoch)
-        train_loss = train_salient_object_detection_segmentation(train_loader, model, train_criterion, optimizer, scheduler, epoch,
-                                                                 logger, config)
-        info(f'train: epoch {epoch:0>3d}, train_loss: {train_loss:.4f}')
-        if epoch % config.save_interval == 0 and local_rank == 0:
-            weights = (config.ema_model.ema_model.module if config.use_ema_model else model.module).state_dict()
-            torch.save(weights, os.path.join(checkpoint_dir, f'epoch_{epoch}.pth'))
-        if epoch in config.eval_epoch or epoch == config.epochs:
-            result_dict = validate_salient_object_detection_segmentation_for_all_dataset(val_loader_list, model, test_criterion,
-                                                                                         config)
-            # the first dataset of the config is the complete validation set: it decides the checkpoint
-            total_result, metric, test_loss = first_dataset_metric(result_dict, config.save_model_metric, metric, test_loss)
-            if total_result:
-                log_info = f'eval: epoch: {epoch:0>3d}\n'
-                for key, value in total_result.items():
-                    log_info += f'{key}: {value}\n'
-                info(log_info)
-        train_time += (time.time() - per_epoch_start_time) / 3600
-        if local_rank == 0:
-            if metric > best_metric and metric <= 100:
-                best_metric = float(metric)               # (a numpy float32: latest.pth holds plain numbers)
-                best = (config.ema_model.ema_model.module if config.use_ema_model else model.module).state_dict()
-                torch.save(best, os.path.join(checkpoint_dir, 'best.pth'))
-            ckpt = {'epoch': epoch, 'time': train_time, 'best_metric': best_metric, 'test_loss': test_loss,
-                    'lr': scheduler.current_lr, 'model_state_dict': model.state_dict(),
-                    'optimizer_state_dict': optimizer.state_dict(), 'scheduler_state_dict': scheduler.state_dict()}
-            if config.use_ema_model:
-                ckpt['ema_model_state_dict'] = config.ema_model.ema_model.state_dict()
-            torch.save(ckpt, os.path.join(checkpoint_dir, 'latest.pth'))
-        info(f'until epoch: {epoch:0>3d}, best_metric: {best_metric:.3f}')
-
-    if local_rank == 0 and os.path.exists(os.path.join(checkpoint_dir, 'best.pth')):
-        os.rename(os.path.join(checkpoint_dir, 'best.pth'),
-                  os.path.join(checkpoint_dir, f'{config.network}-metric{best_metric:.3f}.pth'))
-    info(f'train done. model: {config.network}, train time: {train_time:.3f} hours, best_metric: {best_metric:.3f}')
-    torch.distributed.destroy_process_group()
+    entry.train(parse_args, TASK)
 
 
 if __name__ == '__main__':
