@@ -476,7 +476,7 @@ class RetinaLoss(nn.Module):
         self.box_loss_type = box_loss_type
         self._tables = {}
         # SmoothL1: every decision (assignment, positive count) stays on the device and every shape is static -> the training step
-        # can be captured as one hipGraph (tools/scripts.py _epoch_loop).  The IoU-family box losses index the positive anchors with
+        # can be captured as one hipGraph (tools/loop.py run_epoch).  The IoU-family box losses index the positive anchors with
         # a boolean mask (a host synchronisation and a data-dependent shape): eager only.
         self.capturable = box_loss_type == 'SmoothL1'
 

@@ -1249,7 +1249,9 @@ __global__ __launch_bounds__(SA_THREADS, 2) void sa_bwd_dkv_kernel(const SAParam
             sa_dma16(rw_rs, dst + j * SA_WAVES * 1024, (unsigned)(((q0 + row) * 64 + c4 * 4) * (int)sizeof(float)));
         }
     };
-    const float* rhg = REL == 2 ? p.rel_h + (size_t)bh * p.Nq * p.Sh + 2 * blk : nullptr;
+    // (the block's second kh row does not exist in the last block of an odd Sh: its keys are past Nk and their rows unstored, but
+    // the column index must stay inside the table -- one float past the last row of rel_h is past the allocation)
+    const float* rhg = REL == 2 ? p.rel_h + (size_t)bh * p.Nq * p.Sh + min(2 * blk + ((tid >> 6) & 1), p.Sh - 1) : nullptr;
     auto prefetch = [&](int q0) {
         char* nxt = QO + ((q0 / SA_CHUNK) & 1) * 2 * S::CHUNK_BYTES;
         S::dma(q_rsrc, nxt, p.q_rs, q0, p.Nq, wave, lane);
@@ -1262,7 +1264,7 @@ __global__ __launch_bounds__(SA_THREADS, 2) void sa_bwd_dkv_kernel(const SAParam
             const int rc = min(r, p.Nq - 1);
             pf_l = lsg[rc];
             pf_d = dsg[rc];
-            if constexpr (REL == 2) pf_rh = rhg[(size_t)rc * p.Sh + ((tid >> 6) & 1)];
+            if constexpr (REL == 2) pf_rh = rhg[(size_t)rc * p.Sh];
         }
         if constexpr (EMM) {                               // converted and stored when the chunk becomes current
 #pragma unroll

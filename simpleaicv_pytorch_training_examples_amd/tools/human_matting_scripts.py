@@ -6,23 +6,20 @@
   train_human_matting                       (reference :275-520)
   first_dataset_metric: what the entry script checkpoints by (reference tools/train_human_matting_model.py:215-235)
 
-The training loop is a `step_fn` over tools.scripts._epoch_loop: the reference's skip / accumulation / clipping / scaler / EMA /
+The training loop is a `step_fn` over tools.loop.run_epoch, evaluation the metric code over tools.loop.timed_eval_pass: the reference's skip / accumulation / clipping / scaler / EMA /
 scheduler semantics and its log line with the seven loss names.  The criterion dict is routed as the reference routes it
 (:320-346): the trimap losses read global_pred, the local losses local_pred + mask + trimap, the fusion losses fused_pred + mask,
 CompositionLoss the image, the mask, fg_map, bg_map and fused_pred.  The iteration has static shapes and no host read (the fused
 losses take their gradients as device tensors), so config.use_step_graph captures it whole."""
 import collections
-import time
 
 import numpy as np
 import torch
 from scipy.ndimage import gaussian_filter, label
-from torch.amp.autocast_mode import autocast
 
 from ..engine import any_nonfinite
-from ..SimpleAICV.classification.common import AverageMeter, get_amp_type
+from .loop import begin_training, for_all_datasets, run_epoch, timed_eval_pass
 from .salient_object_detection_scripts import first_dataset_metric  # noqa: F401  (the same rule, one copy)
-from .scripts import _device_of, _epoch_loop
 
 _FOUR_CONNECTED = [[0, 1, 0], [1, 1, 1], [0, 1, 0]]
 
@@ -145,39 +142,21 @@ class EvalMeter:
         self.conn = self.conn / self.sample_num
 
 
-def validate_human_matting_for_all_dataset(val_loader_list, model, criterion, config):
-    result_dict = collections.OrderedDict()
-    for name, loader in zip(config.val_dataset_name_list, val_loader_list):
-        name = '[+]'.join(name).replace('/', '[s]')
-        result_dict[name] = validate_human_matting(loader, model, criterion, config)
-    return result_dict
-
-
 def validate_human_matting(test_loader, model, criterion, config):
-    batch_time, data_time = AverageMeter(), AverageMeter()
     eval_metric = EvalMeter(config)
-    if getattr(config, 'use_ema_model', False):
-        model = config.ema_model.ema_model
-    model.eval()
-    device = _device_of(model)
-    sync = torch.cuda.synchronize if device.type == 'cuda' else (lambda: None)
-    with torch.no_grad():
-        end = time.time()
-        for data in test_loader:
-            images, masks = data['image'].to(device), data['mask'].to(device)
-            sync()
-            data_time.update(time.time() - end)
-            end = time.time()
-            outputs = model(images)[2]                      # the fused prediction is what is evaluated
-            sync()
-            batch_time.update(time.time() - end)
-            eval_metric.add_batch_result(outputs, masks)
-            end = time.time()
+
+    def batch_fn(model, data, device):
+        images, masks = data['image'].to(device), data['mask'].to(device)
+        yield
+        outputs = model(images)[2]                      # the fused prediction is what is evaluated
+        yield
+        eval_metric.add_batch_result(outputs, masks)
+
+    load_ms, inference_ms = timed_eval_pass(test_loader, model, config, batch_fn)
     eval_metric.compute_all_metrics()
-    per_gpu = config.batch_size // config.gpus_num
     result_dict = collections.OrderedDict()
-    result_dict['per_image_load_time'] = f'{data_time.avg / per_gpu * 1000:.3f}ms'
-    result_dict['per_image_inference_time'] = f'{batch_time.avg / per_gpu * 1000:.3f}ms'
+    result_dict['per_image_load_time'] = f'{load_ms:.3f}ms'
+    result_dict['per_image_inference_time'] = f'{inference_ms:.3f}ms'
     result_dict['f_squared_beta_average'] = eval_metric.f_squared_beta_average
     result_dict['f_squared_beta_max'] = eval_metric.f_squared_beta_max
     result_dict['mean_precision'] = eval_metric.precision_average
@@ -192,6 +171,9 @@ def validate_human_matting(test_loader, model, criterion, config):
     result_dict['grad'] = eval_metric.grad
     result_dict['conn'] = eval_metric.conn
     return result_dict
+
+
+validate_human_matting_for_all_dataset = for_all_datasets(validate_human_matting)
 
 
 def matting_losses(criterion, loss_ratio, outputs, images, masks, trimaps, fg_maps, bg_maps):
@@ -220,11 +202,7 @@ def train_human_matting(train_loader, model, criterion, optimizer, scheduler, ep
     '''train human matting model for one epoch (reference tools/human_matting_scripts.py:275-520): `outputs = model(images)`, one
     loss per entry of the criterion dict scaled by config.loss_ratio, and the log line
     `train: epoch 0001, iter [00100, 00937], lr: 0.000100, loss: 6.0674, GlobalTrimapCELoss: 0.6908, GloabelTrimapIouLoss: ..., `.'''
-    model.train()
-    device = _device_of(model)
-    amp_type = get_amp_type(model)
-    if config.local_rank == 0 and getattr(config, 'total_rank', 0) == 0:
-        logger.info(f'use_amp: {config.use_amp}, amp_type: {amp_type}!')
+    device, amp = begin_training(model, logger, config)
 
     def graph_inputs(data):
         return tuple(data[k].to(device, non_blocking=True) for k in _KEYS)
@@ -232,9 +210,9 @@ def train_human_matting(train_loader, model, criterion, optimizer, scheduler, ep
     def step_fn(data):
         images, masks, trimaps, fg_maps, bg_maps = data if isinstance(data, tuple) else graph_inputs(data)
         bad = any_nonfinite(images, masks)
-        with autocast(device_type=device.type, dtype=amp_type, enabled=bool(config.use_amp)):
+        with amp():
             outputs = model(images)
             loss_value = matting_losses(criterion, config.loss_ratio, outputs, images, masks, trimaps, fg_maps, bg_maps)
         return bad, loss_value, images.size(0)
 
-    return _epoch_loop(train_loader, model, optimizer, scheduler, epoch, logger, config, step_fn, 'loss', 5, graph_inputs)
+    return run_epoch(train_loader, model, optimizer, scheduler, epoch, logger, config, step_fn, 'loss', 5, graph_inputs)

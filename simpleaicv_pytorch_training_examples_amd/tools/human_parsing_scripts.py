@@ -7,20 +7,17 @@
   parsing_metrics: the per-class precision / recall / IoU / Dice arithmetic of validate_human_parsing (:139-203) on its own
   first_dataset_metric: what the entry script checkpoints by (reference tools/train_human_parsing_model.py)
 
-The training loop is a `step_fn` over tools.scripts._epoch_loop: the reference's skip / accumulation / clipping / scaler / EMA /
+The training loop is a `step_fn` over tools.loop.run_epoch: the reference's skip / accumulation / clipping / scaler / EMA /
 scheduler semantics and its log line with one value per loss name.  All losses of the criterion dict read the same prediction, so
 on the device they share one pass of ops.pixel_class_terms each way.  The iteration has static shapes and no host read, so
-config.use_step_graph captures it whole."""
+config.use_step_graph captures it whole.  The evaluation pass is the one semantic segmentation makes
+(tools.scripts.timed_class_area_pass)."""
 import collections
-import time
-
-import torch
-from torch.amp.autocast_mode import autocast
 
 from ..engine import any_nonfinite
-from ..SimpleAICV.classification.common import AverageMeter, get_amp_type
+from .loop import begin_training, for_all_datasets, run_epoch
 from .salient_object_detection_scripts import first_dataset_metric  # noqa: F401  (the same rule, one copy)
-from .scripts import _device_of, _epoch_loop, semantic_segmentation_areas
+from .scripts import timed_class_area_pass
 
 
 def parsing_metrics(areas):
@@ -53,55 +50,22 @@ def parsing_metrics(areas):
     return result
 
 
-def validate_human_parsing_for_all_dataset(val_loader_list, model, criterion, config):
-    result_dict = collections.OrderedDict()
-    for name, loader in zip(config.val_dataset_name_list, val_loader_list):
-        name = '[+]'.join(name).replace('/', '[s]')
-        result_dict[name] = validate_human_parsing(loader, model, criterion, config)
-    return result_dict
-
-
 def validate_human_parsing(test_loader, model, criterion, config):
     """reference :43-204: loss by the test criterion, argmax over the classes, the top-left int(size) crop, per-class areas
     accumulated on the device in float64 (tools.scripts.semantic_segmentation_areas), then parsing_metrics."""
-    batch_time, data_time, losses = AverageMeter(), AverageMeter(), AverageMeter()
-    if getattr(config, 'use_ema_model', False):
-        model = config.ema_model.ema_model
-    model.eval()
-    device = _device_of(model)
-    sync = torch.cuda.synchronize if device.type == 'cuda' else (lambda: None)
-    areas = torch.zeros((4, config.num_classes), dtype=torch.float64, device=device)
-    with torch.no_grad():
-        end = time.time()
-        for data in test_loader:
-            images, masks, sizes = data['image'].to(device), data['mask'].to(device), data['size']
-            sync()
-            data_time.update(time.time() - end)
-            end = time.time()
-            outputs = model(images)
-            sync()
-            batch_time.update(time.time() - end)
-            losses.update(float(criterion(outputs, masks)), images.size(0))
-            areas += semantic_segmentation_areas(torch.argmax(outputs, dim=1), masks, sizes, config.num_classes)
-            end = time.time()
-    per_gpu = config.batch_size // config.gpus_num
-    result_dict = collections.OrderedDict()
-    result_dict['test_loss'] = losses.avg
-    result_dict['per_image_load_time'] = f'{data_time.avg / per_gpu * 1000:.3f}ms'
-    result_dict['per_image_inference_time'] = f'{batch_time.avg / per_gpu * 1000:.3f}ms'
-    result_dict.update(parsing_metrics(areas.cpu().tolist()))
+    result_dict, areas = timed_class_area_pass(test_loader, model, criterion, config)
+    result_dict.update(parsing_metrics(areas))
     return result_dict
+
+
+validate_human_parsing_for_all_dataset = for_all_datasets(validate_human_parsing)
 
 
 def train_human_parsing(train_loader, model, criterion, optimizer, scheduler, epoch, logger, config):
     '''train human parsing model for one epoch (reference :207-394): `outputs = model(images)`, one loss per entry of the criterion
     dict scaled by config.loss_ratio, a batch with inf / nan images, masks, loss or gradients skipped, and the log line
     `train: epoch 0001, iter [00100, 00158], lr: 0.000100, loss: 1.9042, CELoss: 1.2042, IoULoss: 0.7000, `.'''
-    model.train()
-    device = _device_of(model)
-    amp_type = get_amp_type(model)
-    if config.local_rank == 0 and getattr(config, 'total_rank', 0) == 0:
-        logger.info(f'use_amp: {config.use_amp}, amp_type: {amp_type}!')
+    device, amp = begin_training(model, logger, config)
 
     def step_fn(data):
         if isinstance(data, tuple):                      # captured step: static device buffers
@@ -110,11 +74,11 @@ def train_human_parsing(train_loader, model, criterion, optimizer, scheduler, ep
             images = data['image'].to(device, non_blocking=True)
             masks = data['mask'].to(device, non_blocking=True)
         bad = any_nonfinite(images, masks)
-        with autocast(device_type=device.type, dtype=amp_type, enabled=bool(config.use_amp)):
+        with amp():
             outputs = model(images)
             loss_value = {name: config.loss_ratio[name] * criterion[name](outputs, masks) for name in criterion.keys()}
         return bad, loss_value, images.size(0)
 
     def graph_inputs(data):
         return (data['image'].to(device, non_blocking=True), data['mask'].to(device, non_blocking=True))
-    return _epoch_loop(train_loader, model, optimizer, scheduler, epoch, logger, config, step_fn, 'loss', 5, graph_inputs)
+    return run_epoch(train_loader, model, optimizer, scheduler, epoch, logger, config, step_fn, 'loss', 5, graph_inputs)

@@ -6,19 +6,17 @@
   train_salient_object_detection_segmentation                      (reference :178-368)
   first_dataset_metric: what the entry script checkpoints by       (reference tools/train_salient_object_detection_model.py:215-235)
 
-The training loop is a `step_fn` over tools.scripts._epoch_loop: the reference's skip / accumulation / clipping / scaler / EMA /
+The training loop is a `step_fn` over tools.loop.run_epoch: the reference's skip / accumulation / clipping / scaler / EMA /
 scheduler semantics and its log line.  The iteration has static shapes and no host read (the fused mask statistics take their
-gradient as a device tensor), so config.use_step_graph captures it whole, as train_semantic_segmentation does."""
+gradient as a device tensor), so config.use_step_graph captures it whole, as train_semantic_segmentation does.  Evaluation is
+the metric code over tools.loop.timed_eval_pass."""
 import collections
-import time
 
 import numpy as np
 import torch
-from torch.amp.autocast_mode import autocast
 
 from ..engine import any_nonfinite
-from ..SimpleAICV.classification.common import AverageMeter, get_amp_type
-from .scripts import _device_of, _epoch_loop
+from .loop import begin_training, for_all_datasets, run_epoch, timed_eval_pass
 
 
 class EvalMeter:
@@ -81,39 +79,21 @@ class EvalMeter:
         self.recall_max = np.max(self.recall_list)
 
 
-def validate_salient_object_detection_segmentation_for_all_dataset(val_loader_list, model, criterion, config):
-    result_dict = collections.OrderedDict()
-    for name, loader in zip(config.val_dataset_name_list, val_loader_list):
-        name = '[+]'.join(name).replace('/', '[s]')
-        result_dict[name] = validate_salient_object_detection_segmentation(loader, model, criterion, config)
-    return result_dict
-
-
 def validate_salient_object_detection_segmentation(test_loader, model, criterion, config):
-    batch_time, data_time = AverageMeter(), AverageMeter()
     eval_metric = EvalMeter(config)
-    if getattr(config, 'use_ema_model', False):
-        model = config.ema_model.ema_model
-    model.eval()
-    device = _device_of(model)
-    sync = torch.cuda.synchronize if device.type == 'cuda' else (lambda: None)
-    with torch.no_grad():
-        end = time.time()
-        for data in test_loader:
-            images, masks = data['image'].to(device), data['mask'].to(device)
-            sync()
-            data_time.update(time.time() - end)
-            end = time.time()
-            outputs = model(images)
-            sync()
-            batch_time.update(time.time() - end)
-            eval_metric.add_batch_result(outputs, masks)
-            end = time.time()
+
+    def batch_fn(model, data, device):
+        images, masks = data['image'].to(device), data['mask'].to(device)
+        yield
+        outputs = model(images)
+        yield
+        eval_metric.add_batch_result(outputs, masks)
+
+    load_ms, inference_ms = timed_eval_pass(test_loader, model, config, batch_fn)
     eval_metric.compute_all_metrics()
-    per_gpu = config.batch_size // config.gpus_num
     result_dict = collections.OrderedDict()
-    result_dict['per_image_load_time'] = f'{data_time.avg / per_gpu * 1000:.3f}ms'
-    result_dict['per_image_inference_time'] = f'{batch_time.avg / per_gpu * 1000:.3f}ms'
+    result_dict['per_image_load_time'] = f'{load_ms:.3f}ms'
+    result_dict['per_image_inference_time'] = f'{inference_ms:.3f}ms'
     result_dict['f_squared_beta_average'] = eval_metric.f_squared_beta_average
     result_dict['f_squared_beta_max'] = eval_metric.f_squared_beta_max
     result_dict['mean_precision'] = eval_metric.precision_average
@@ -123,6 +103,9 @@ def validate_salient_object_detection_segmentation(test_loader, model, criterion
     result_dict['miou_average'] = eval_metric.miou_average
     result_dict['miou_max'] = eval_metric.miou_max
     return result_dict
+
+
+validate_salient_object_detection_segmentation_for_all_dataset = for_all_datasets(validate_salient_object_detection_segmentation)
 
 
 def first_dataset_metric(result_dict, save_model_metric, metric=0, test_loss=0):
@@ -141,11 +124,7 @@ def train_salient_object_detection_segmentation(train_loader, model, criterion, 
     '''train salient object detection segmentation model for one epoch (reference tools/salient_object_detection_scripts.py:178-368):
     `outputs = model(images)`, one loss per entry of the criterion dict scaled by config.loss_ratio, and the log line
     `train: epoch 0001, iter [00100, 00631], lr: 0.000100, loss: 1.2042, BCELoss: 0.6021, BCEIouloss: 0.6021, `.'''
-    model.train()
-    device = _device_of(model)
-    amp_type = get_amp_type(model)
-    if config.local_rank == 0 and getattr(config, 'total_rank', 0) == 0:
-        logger.info(f'use_amp: {config.use_amp}, amp_type: {amp_type}!')
+    device, amp = begin_training(model, logger, config)
 
     def step_fn(data):
         if isinstance(data, tuple):                      # captured step: static device buffers
@@ -154,11 +133,11 @@ def train_salient_object_detection_segmentation(train_loader, model, criterion, 
             images = data['image'].to(device, non_blocking=True)
             masks = data['mask'].to(device, non_blocking=True)
         bad = any_nonfinite(images, masks)
-        with autocast(device_type=device.type, dtype=amp_type, enabled=bool(config.use_amp)):
+        with amp():
             outputs = model(images)
             loss_value = {name: config.loss_ratio[name] * criterion[name](outputs, masks) for name in criterion.keys()}
         return bad, loss_value, images.size(0)
 
     def graph_inputs(data):
         return (data['image'].to(device, non_blocking=True), data['mask'].to(device, non_blocking=True))
-    return _epoch_loop(train_loader, model, optimizer, scheduler, epoch, logger, config, step_fn, 'loss', 5, graph_inputs)
+    return run_epoch(train_loader, model, optimizer, scheduler, epoch, logger, config, step_fn, 'loss', 5, graph_inputs)

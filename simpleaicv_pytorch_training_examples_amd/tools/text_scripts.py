@@ -3,10 +3,10 @@ images [B, 3, H, W] to per-frame logits [B, T, num_classes + 1].
 
 train_text_recognition (:894-...): `outputs = model(images)`, the permuted [T, B, C] view goes to the criterion dict
 ({'CTCLoss': ...} in the reference config, 'ACELoss' also known) scaled by config.loss_ratio; accumulation, skip of a non-finite
-batch, scaler, clipping, EMA, scheduler and the reference's log line come from tools.scripts._epoch_loop.  On the device CTCLoss
+batch, scaler, clipping, EMA, scheduler and the reference's log line come from tools.loop.run_epoch.  On the device CTCLoss
 is ops.ctc_loss (csrc/ctc.hip): labels are encoded on the host by config.converter and copied over, nothing is read back.  The
 iteration has no host read and nn.LSTM captures unchanged, so config.use_step_graph replays it as one hipGraph -- for batches of
-ONE width and accumulation_steps 1 (what tools.scripts._epoch_loop's captured step asks for); the reference config's
+ONE width and accumulation_steps 1 (what tools.loop.run_epoch's captured step asks for); the reference config's
 accumulation_steps 2 and batches of changing width run eagerly.
 
 test_text_recognition_for_all_dataset (:31-...): one pass per validation set (the reference makes four): test_loss by the test
@@ -16,18 +16,17 @@ final_edit_distance (ICDAR2019 normalised edit distance) and lcs_precision / lcs
 distance and LCS are SimpleAICV.text_recognition.common's.  The reference's order precision / recall and the per-table LCS figures
 (digits, letters, the three Chinese tables) are not computed, nor its `ignore_threhold` (-1 below 1000 target characters)."""
 import collections
-import time
 
 import torch
 import torch.nn.functional as F
-from torch.amp.autocast_mode import autocast
 
 from .. import ops
 from ..engine import any_nonfinite
-from ..SimpleAICV.classification.common import AverageMeter, get_amp_type
+from ..SimpleAICV.classification.common import AverageMeter
 from ..SimpleAICV.text_recognition.common import edit_distance, lcs_length
+from .loop import begin_training, for_all_datasets, run_epoch, timed_eval_pass
 from .salient_object_detection_scripts import first_dataset_metric  # noqa: F401  (checkpoints go by lcs_precision of the first set)
-from .scripts import _device_of, _epoch_loop, all_reduce_operation_in_group_for_variables
+from .scripts import all_reduce_operation_in_group_for_variables
 
 
 def text_losses(criterion, loss_ratio, outputs, trans_targets, input_lengths, target_lengths):
@@ -82,51 +81,42 @@ def string_counts(pred_strs, targets, keep_characters, garbage_char, case_insens
 def test_text_recognition_for_all_dataset(val_loader_list, model, criterion, config):
     if getattr(config, 'use_ema_model', False):
         model = config.ema_model.ema_model
-    result_dict = collections.OrderedDict()
-    for name, loader in zip(config.val_dataset_name_list, val_loader_list):
-        name = '[+]'.join(name).replace('/', '[s]')
-        result_dict[name] = test_text_recognition_for_per_sub_dataset(loader, model, criterion, config)
-    return result_dict
+    return for_all_datasets(test_text_recognition_for_per_sub_dataset)(val_loader_list, model, criterion, config)
 
 
 def test_text_recognition_for_per_sub_dataset(val_loader, model, criterion, config):
-    batch_time, data_time, losses = AverageMeter(), AverageMeter(), AverageMeter()
+    losses = AverageMeter()
     converter = config.converter
     keep = ''.join(config.all_char_table)
-    model.eval()
-    device = _device_of(model)
-    sync = torch.cuda.synchronize if device.type == 'cuda' else (lambda: None)
     total = collections.Counter()
     total_strs = 0
-    with torch.no_grad():
-        end = time.time()
-        for data in val_loader:
-            images, targets = data['image'].to(device), data['label']
-            trans_targets, target_lengths = converter.encode(targets)
-            trans_targets, target_lengths = trans_targets.to(device), target_lengths.to(device)
-            sync()
-            data_time.update(time.time() - end)
-            end = time.time()
-            outputs = model(images)
-            sync()
-            batch_time.update(time.time() - end)
-            input_lengths = torch.full((outputs.shape[0],), outputs.shape[1], dtype=torch.int32, device=device)
-            loss = criterion(outputs.permute(1, 0, 2), trans_targets, input_lengths, target_lengths)
-            [loss] = all_reduce_operation_in_group_for_variables([loss], torch.distributed.ReduceOp.SUM, getattr(config, 'group', None))
-            losses.update(float(loss) / float(config.gpus_num), images.size(0))
-            index, _prob = greedy_decode(outputs, input_lengths)
-            pred_strs = converter.decode(index, input_lengths.cpu().numpy())
-            total.update(string_counts(pred_strs, targets, keep, converter.garbage_char))
-            total_strs += images.size(0)
-            end = time.time()
+
+    def batch_fn(model, data, device):
+        nonlocal total_strs
+        images, targets = data['image'].to(device), data['label']
+        trans_targets, target_lengths = converter.encode(targets)
+        trans_targets, target_lengths = trans_targets.to(device), target_lengths.to(device)
+        yield
+        outputs = model(images)
+        yield
+        input_lengths = torch.full((outputs.shape[0],), outputs.shape[1], dtype=torch.int32, device=device)
+        loss = criterion(outputs.permute(1, 0, 2), trans_targets, input_lengths, target_lengths)
+        [loss] = all_reduce_operation_in_group_for_variables([loss], torch.distributed.ReduceOp.SUM, getattr(config, 'group', None))
+        losses.update(float(loss) / float(config.gpus_num), images.size(0))
+        index, _prob = greedy_decode(outputs, input_lengths)
+        pred_strs = converter.decode(index, input_lengths.cpu().numpy())
+        total.update(string_counts(pred_strs, targets, keep, converter.garbage_char))
+        total_strs += images.size(0)
+
+    # (the model is the one the caller hands over: the ..._for_all_dataset wrapper has made the EMA switch)
+    load_ms, inference_ms = timed_eval_pass(val_loader, model, config, batch_fn, ema=False)
     keys = ['correct', 'not_included', 'ne_distance', 'lcs', 'pred_chars', 'target_chars']
     values = all_reduce_operation_in_group_for_variables([total[k] for k in keys] + [total_strs], torch.distributed.ReduceOp.SUM,
                                                          getattr(config, 'group', None))
     total, total_strs = dict(zip(keys, values[:-1])), values[-1]
-    per_gpu = config.batch_size // config.gpus_num
     result = collections.OrderedDict()
-    result['per_image_load_time'] = data_time.avg / per_gpu * 1000
-    result['per_image_inference_time'] = batch_time.avg / per_gpu * 1000
+    result['per_image_load_time'] = load_ms
+    result['per_image_inference_time'] = inference_ms
     result['test_loss'] = losses.avg
     result['str_acc'] = total['correct'] / float(total_strs) * 100 if total_strs else 0
     result['not_included_str_percent'] = total['not_included'] / float(total_strs) * 100 if total_strs else 0
@@ -139,11 +129,7 @@ def test_text_recognition_for_per_sub_dataset(val_loader, model, criterion, conf
 def train_text_recognition(train_loader, model, criterion, optimizer, scheduler, epoch, logger, config):
     '''train a text recognition model for one epoch; the log line is
     `train: epoch 0001, iter [00050, 00158], lr: 0.000100, loss: 12.9042, CTCLoss: 12.9042, `.'''
-    model.train()
-    device = _device_of(model)
-    amp_type = get_amp_type(model)
-    if config.local_rank == 0 and getattr(config, 'total_rank', 0) == 0:
-        logger.info(f'use_amp: {config.use_amp}, amp_type: {amp_type}!')
+    device, amp = begin_training(model, logger, config)
 
     def graph_inputs(data):
         trans_targets, target_lengths = config.converter.encode(data['label'])
@@ -154,11 +140,11 @@ def train_text_recognition(train_loader, model, criterion, optimizer, scheduler,
         # (a tuple: the static device buffers of the captured step)
         images, trans_targets, target_lengths = data if isinstance(data, tuple) else graph_inputs(data)
         bad = any_nonfinite(images)
-        with autocast(device_type=device.type, dtype=amp_type, enabled=bool(config.use_amp)):
+        with amp():
             outputs = model(images)                                          # [B, T, C]
             input_lengths = torch.full((outputs.shape[0],), outputs.shape[1], dtype=torch.int32, device=device)
             loss_value = text_losses(criterion, config.loss_ratio, outputs.permute(1, 0, 2), trans_targets, input_lengths,
                                      target_lengths)
         return bad, loss_value, images.size(0)
 
-    return _epoch_loop(train_loader, model, optimizer, scheduler, epoch, logger, config, step_fn, 'loss', 5, graph_inputs)
+    return run_epoch(train_loader, model, optimizer, scheduler, epoch, logger, config, step_fn, 'loss', 5, graph_inputs)

@@ -1,4 +1,4 @@
-"""tools/text_scripts.py on the GPU: train_text_recognition over _epoch_loop with accumulation 1 and 2, fused against composed
+"""tools/text_scripts.py on the GPU: train_text_recognition over tools/loop.py run_epoch with accumulation 1 and 2, fused against composed
 CTCLoss trajectories, test_text_recognition_for_all_dataset and its keys, a variable-width batch -- on a stand-in with the
 model's contract (images [B, 3, 32, W] -> logits [B, W / 4, C]): two linear layers over groups of four image columns, torch ops
 only, so that what is under test is the loops, the CTC loss and the greedy decode, and the two routes can be compared without
