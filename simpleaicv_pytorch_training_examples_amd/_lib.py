@@ -1,289 +1,116 @@
-"""ctypes binding of libsaicv_hip.so (include/saicv_hip.h).
+"""ctypes binding of libsaicv_hip.so, read from include/saicv_hip.h at import.
 
 The product path has no CPU fallback: if the library is missing, or a tensor is not on a
 HIP device, the call raises.  PyTorch is used only for device memory and streams.
 """
 import ctypes
+import functools
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_void_p
+import re
+from ctypes import POINTER, Structure, c_char_p, c_void_p
 
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libsaicv_hip.so')
+HEADER_PATH = os.path.join(os.path.dirname(HERE), 'include', 'saicv_hip.h')
 
-BF16, F32 = 0, 1
-
-
-class ConvDesc(Structure):
-    _fields_ = [('N', c_int), ('H', c_int), ('W', c_int), ('C', c_int), ('K', c_int), ('R', c_int),
-                ('S', c_int), ('stride', c_int), ('pad', c_int), ('OH', c_int), ('OW', c_int),
-                ('dtype', c_int)]
-
-
-_P = c_void_p
-_PD = POINTER(ConvDesc)
+_SCALARS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'long long': ctypes.c_longlong, 'unsigned int': ctypes.c_uint,
+            'unsigned long long': ctypes.c_ulonglong, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float,
+            'double': ctypes.c_double}
+_POINTEES = set(_SCALARS) | {'void', 'unsigned char', 'uint8_t', 'int32_t'}
+_KEYWORDS = {w for t in _POINTEES | {'const', 'char', 'short', 'struct'} for w in t.split()}
+_DECLARATOR = re.compile(r'(?:const\s+)?([A-Za-z_][\w ]*?)\s*(\**)\s*(\w+)(?:\[(\d+)\])?')
 
 
-class AttnDesc(Structure):
-    """saicv_attn_desc (include/saicv_hip.h): streaming attention problem descriptor."""
-    _fields_ = [('q', _P), ('k', _P), ('v', _P),
-                ('q_rs', c_long), ('k_rs', c_long), ('v_rs', c_long),
-                ('q_bs', c_long), ('k_bs', c_long), ('v_bs', c_long),
-                ('out', _P), ('o_rs', c_long), ('o_bs', c_long),
-                ('dout', _P), ('dq', _P), ('dk', _P), ('dv', _P),
-                ('lse', _P), ('dsum', _P), ('key_bias', _P), ('rel_h', _P), ('rel_w', _P),
-                ('d_rel_h', _P), ('d_rel_w', _P),
-                ('Sh', c_int), ('Sw', c_int), ('B', c_int), ('H', c_int), ('Nq', c_int), ('Nk', c_int),
-                ('scale', c_float), ('dropout_p', c_float), ('seed', ctypes.c_uint32), ('seed_device', _P)]
+@functools.lru_cache(maxsize=None)
+def struct_ptr(cls):
+    """argtype of a `const saicv_x*` parameter: byref() of that struct and no other (a host descriptor), or None / an address
+    (a device array of them)."""
+    typed = POINTER(cls)
+
+    class StructPtr:
+        struct = cls
+
+        @staticmethod
+        def from_param(value):
+            return c_void_p(value) if value is None or isinstance(value, int) else typed.from_param(value)
+    return StructPtr
 
 
-_PA = POINTER(AttnDesc)
+def _ctype(base, stars, structs, opaque, text):
+    base = ' '.join(base.split())
+    if not stars:
+        if base in _SCALARS:
+            return _SCALARS[base]
+        if base in structs:
+            return structs[base]
+    elif base == 'char' and stars == '*':
+        return c_char_p
+    elif base in structs and stars == '*':
+        return struct_ptr(structs[base])
+    elif base in _POINTEES or base in opaque:
+        return c_void_p
+    raise ValueError(f'saicv_hip.h: unknown type {base + stars!r} in {text!r}')
 
 
-class DgradFuse(Structure):
-    """saicv_dgrad_fuse (include/saicv_hip.h)"""
-    _fields_ = [('addend', c_void_p), ('addend_gate', c_void_p), ('bn_y', c_void_p), ('bn_mask', c_void_p),
-                ('bn_mean', c_void_p), ('bn_invstd', c_void_p), ('part_g', c_void_p), ('part_gx', c_void_p),
-                ('part_rows', c_int), ('reserved', c_int)]
+def _declarator(text):
+    m = _DECLARATOR.fullmatch(text.strip())
+    if not m or m.group(3) in _KEYWORDS:          # `long long` without a name must not read as a `long` called long
+        raise ValueError(f'saicv_hip.h: cannot split {text!r}')
+    return m.groups()
 
 
-_PF = POINTER(DgradFuse)
+def parse_header(text):
+    """-> (constants {'SAICV_X': n}, structs {'saicv_x': Structure}, signatures {'saicv_f': (restype, argtypes)}).
+    Reads `#define SAICV_X n`, `typedef struct ... { ... } name;` and `ret saicv_name(params);`; anything else raises."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    text = re.sub(r'^[ \t]*#\s*ifdef\s+__cplusplus\b.*?^[ \t]*#\s*endif[^\n]*$', ' ', text, flags=re.S | re.M)
+    constants = {k: int(v, 0) for k, v in re.findall(r'^[ \t]*#\s*define\s+(SAICV_\w+)\s+(-?\w+)[ \t]*$', text, flags=re.M)}
+    text = re.sub(r'^[ \t]*#[^\n]*$', ' ', text, flags=re.M)
+    opaque = set()
+    for tag, name in re.findall(r'\btypedef\s+struct\s+(\w+)\s+(\w+)\s*;', text):
+        if tag != name:
+            raise ValueError(f'saicv_hip.h: opaque typedef {tag!r} is named {name!r}')
+        opaque.add(name)
+    text = re.sub(r'\btypedef\s+struct\s+\w+\s+\w+\s*;', ' ', text)
+    structs = {}
+
+    def struct(m):
+        name, fields = m.group(2), []
+        for stmt in filter(None, (s.strip() for s in m.group(1).split(';'))):
+            first, *more = stmt.split(',')
+            base, stars, field, count = _declarator(first)
+            if stars and more:
+                raise ValueError(f'saicv_hip.h: one pointer member per statement, got {stmt!r}')
+            ct = _ctype(base, stars, structs, opaque, stmt)
+            fields.append((field, ct * int(count) if count else ct))
+            for extra in more:
+                if not re.fullmatch(r'\s*\w+\s*', extra):
+                    raise ValueError(f'saicv_hip.h: cannot split {stmt!r}')
+                fields.append((extra.strip(), ct))
+        structs[name] = type(''.join(w.capitalize() for w in name.split('_')[1:]), (Structure,),
+                             {'_fields_': fields, '__doc__': f'{name} (include/saicv_hip.h)'})
+        return ' '
+    text = re.sub(r'\btypedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(\w+)\s*;', struct, text)
+    signatures = {}
+    for stmt in filter(None, (s.strip() for s in text.split(';'))):
+        m = re.fullmatch(r'([^()]+)\(([^()]*)\)', stmt)
+        if not m:
+            raise ValueError(f'saicv_hip.h: cannot split {stmt!r}')
+        base, stars, name, count = _declarator(m.group(1))
+        params = [] if m.group(2).strip() == 'void' else [_declarator(p) for p in m.group(2).split(',')]
+        if count or not name.startswith('saicv_') or name in signatures or any(p[3] for p in params):
+            raise ValueError(f'saicv_hip.h: cannot bind {stmt!r}')
+        signatures[name] = (_ctype(base, stars, structs, opaque, stmt), [_ctype(b, s, structs, opaque, stmt) for b, s, _, _ in params])
+    return constants, structs, signatures
 
 
-class PlanQuery(Structure):
-    """saicv_plan_query (include/saicv_hip.h)"""
-    _fields_ = [('op', c_int), ('conv', ConvDesc), ('dtype', c_int), ('M', c_int), ('K', c_int), ('N', c_int),
-                ('out_f32', c_int), ('bias', c_int), ('stats', c_int), ('addend', c_int), ('row_scale', c_int),
-                ('bn_sums', c_int), ('act_mode', c_int)]
-
-
-class Plan(Structure):
-    """saicv_plan (include/saicv_hip.h)"""
-    _fields_ = [(n, c_int) for n in ('route', 'tile', 'bm', 'bn', 'kc8', 'plain', 'out_f32', 'dma', 'blocks', 'stat_rows',
-                                     'splits', 'rt_per', 'total_rt', 'rows_per_step')]
-
-
-PLAN_CONV_FWD, PLAN_CONV_DGRAD, PLAN_CONV_WGRAD, PLAN_LINEAR_FWD, PLAN_LINEAR_DGRAD, PLAN_LINEAR_WGRAD = range(6)
-ROUTE_TILED, ROUTE_PW_STREAM, ROUTE_PW3_STREAM, ROUTE_TN = range(4)
-
-
-class PackDesc(Structure):
-    """saicv_pack_desc (include/saicv_hip.h)"""
-    _fields_ = [('w', c_void_p), ('sO', c_long), ('sI', c_long), ('sR', c_long), ('sS', c_long),
-                ('O', c_int), ('I', c_int), ('R', c_int), ('S', c_int), ('Ip', c_int), ('Op', c_int),
-                ('wf', c_void_p), ('wd', c_void_p), ('tile_begin', c_int), ('tiles_i', c_int), ('tiles_o', c_int),
-                ('tile', c_int)]
-
-class MixPlan(Structure):
-    """saicv_mix_plan (include/saicv_hip.h)"""
-    _fields_ = [('mode', c_int), ('yl', c_int), ('yh', c_int), ('xl', c_int), ('xh', c_int), ('lam', ctypes.c_float),
-                ('one_minus_lam', ctypes.c_float), ('label_lam', ctypes.c_float), ('label_one_minus_lam', ctypes.c_float)]
-
-
-class EraseBox(Structure):
-    """saicv_erase_box (include/saicv_hip.h)"""
-    _fields_ = [('b', c_int), ('top', c_int), ('left', c_int), ('h', c_int), ('w', c_int), ('mode', c_int), ('color', ctypes.c_float * 4)]
-
-
-# name -> (restype, argtypes); mirrors include/saicv_hip.h one to one
-SIGNATURES = {
-    'saicv_version': (c_int, []),
-    'saicv_last_error_string': (c_char_p, []),
-    'saicv_set_deterministic': (c_int, [c_int]),
-    'saicv_get_deterministic': (c_int, []),
-    'saicv_deterministic_prepare': (c_int, [_P]),
-    'saicv_pack_input': (c_int, [c_int, _P, c_long, c_long, c_long, c_long, _P, c_int, c_int, c_int, c_int, c_int, _P]),
-    'saicv_pack_weight': (c_int, [c_int, _P, c_long, c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
-    'saicv_unpack_wgrad': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_long, c_long, c_long, c_long, c_int, _P]),
-    'saicv_pack_weight_batched': (c_int, [c_int, _P, c_int, c_int, _P]),
-    'saicv_pack_input_s2d': (c_int, [c_int, _P, c_long, c_long, c_long, c_long, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
-    'saicv_pack_weight_s2d': (c_int, [c_int, _P, c_long, c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_int, _P, _P]),
-    'saicv_unpack_wgrad_s2d': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_long, c_long, c_long, c_long, c_int, _P]),
-    'saicv_conv2d_stat_rows': (c_int, [_PD]),
-    'saicv_conv2d_fwd': (c_int, [_PD, _P, _P, _P, _P, c_int, _P, _P, _P]),
-    'saicv_conv2d_dgrad': (c_int, [_PD, _P, _P, _P, _P]),
-    'saicv_conv2d_wgrad': (c_int, [_PD, _P, _P, _P, _P]),
-    'saicv_conv2d_wgrad_bias': (c_int, [_PD, _P, _P, _P, _P, _P]),
-    'saicv_colsum': (c_int, [c_int, _P, c_int, c_int, _P, _P]),
-    'saicv_linear_fwd': (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P]),
-    'saicv_linear_dgrad': (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, _P, _P]),
-    'saicv_linear_wgrad': (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    'saicv_conv2d_dgrad_add': (c_int, [_PD, _P, _P, _P, _P, _P]),
-    'saicv_conv2d_dgrad_stat_rows': (c_int, [_PD]),
-    'saicv_conv2d_dgrad_fused': (c_int, [_PD, _P, _P, _PF, _P, _P]),
-    'saicv_c3_bwd_stream_ok': (c_int, [c_int, c_int, c_int, c_int]),
-    'saicv_c3_bwd_stream_rows': (c_int, [c_int, c_int, c_int]),
-    'saicv_c3_bwd_stream_ws_floats': (c_size_t, [c_int, c_int, c_int]),
-    'saicv_c3_bwd_stream': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, c_int, _P, _P, _P, _PF, _P, _P, c_int, c_int, c_int, _P]),
-    'saicv_igemm_plan': (c_int, [POINTER(PlanQuery), POINTER(Plan)]),
-    'saicv_conv2d_fwd_stats': (c_int, [_PD, _P, _P, _P, _P, _P, c_int, _P]),
-    'saicv_bn_act_fwd_stats': (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_double, _P, _P, _P, _P, c_double, c_double, _P, _P, _P,
-                                       c_size_t, c_int, c_int, _P, _P]),
-    'saicv_bn_act_fwd_join': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_double, _P, _P, _P, _P, c_double, c_double,
-                                      _P, _P, _P, c_size_t, c_int, c_int, _P, _P]),
-    'saicv_bn_act_bwd_inline': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, c_size_t, c_int, c_int,
-                                        c_int, _P]),
-    'saicv_bn_act_bwd_from_partials': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, c_size_t, c_int,
-                                               c_int, c_int, _P, _P]),
-    'saicv_row_scale': (c_int, [c_int, _P, _P, _P, c_size_t, c_int, c_int, _P]),
-    'saicv_bn_ws_floats': (c_size_t, [c_int]),
-    'saicv_bn_finalize_fwd': (c_int, [_P, _P, c_int, c_int, c_double, _P, _P, _P, _P, c_double, c_double, _P, _P, _P, _P, _P, _P, _P]),
-    'saicv_bn_eval_coeffs': (c_int, [c_int, _P, _P, _P, _P, c_double, _P, _P, _P]),
-    'saicv_bn_act_fwd': (c_int, [c_int, _P, _P, _P, _P, _P, c_size_t, c_int, c_int, _P, _P]),
-    'saicv_bn_bwd_ws_floats': (c_size_t, [c_size_t, c_int, c_int]),
-    'saicv_bn_act_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, c_int, c_int, c_int, _P, _P]),
-    'saicv_maxpool_fwd': (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
-    'saicv_maxpool_bwd': (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
-    'saicv_bn_relu_maxpool_fwd': (c_int, [c_int, _P, _P, _P, _P, _P] + [c_int] * 9 + [_P]),
-    'saicv_bn_relu_maxpool_fwd_keep': (c_int, [c_int, _P, _P, _P, _P, _P, _P] + [c_int] * 9 + [_P]),
-    'saicv_bn_relu_maxpool_bwd_sums': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P] + [c_int] * 4 + [_P]),
-    'saicv_bn_relu_maxpool_bwd_apply': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int] + [c_int] * 9 + [_P]),
-    'saicv_stem_bwd_stream_ok': (c_int, [c_int] * 11),
-    'saicv_stem_bwd_stream_ws_floats': (c_size_t, [c_int, c_int, c_int]),
-    'saicv_stem_bwd_stream': (c_int, [c_int] + [_P] * 13 + [c_int, _P] + [c_int] * 10 + [_P]),
-    'saicv_bn_relu_maxpool_bwd_ws_floats': (c_size_t, [c_int]),
-    'saicv_bn_relu_maxpool_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P] + [c_int] * 9 + [_P]),
-    'saicv_avgpool_fwd': (c_int, [c_int, _P, _P, c_int, c_int, c_int, _P]),
-    'saicv_avgpool_bwd': (c_int, [c_int, _P, _P, c_int, c_int, c_int, _P]),
-    'saicv_softmax_ce_fwd': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
-    'saicv_scale_by_scalar': (c_int, [c_int, _P, _P, _P, c_size_t, _P]),
-    'saicv_sgd_flat': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    'saicv_adamw_flat': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    'saicv_muon_prepare': (c_int, [_P] * 12 + [c_size_t, _P]),
-    'saicv_muon_newton_schulz': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_int, _P, _P]),
-    'saicv_muon_apply': (c_int, [_P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    'saicv_grad_stats': (c_int, [_P, c_size_t, _P, _P, _P]),
-    'saicv_grad_clip_scale': (c_int, [_P, c_size_t, _P, _P, c_double, _P]),
-    'saicv_grad_clip_value': (c_int, [_P, c_size_t, _P, c_double, _P]),
-    'saicv_scaler_update': (c_int, [_P, _P, c_double, c_double, c_int, _P]),
-    # transformer kernels (tfm.hip)
-    'saicv_layernorm_fwd': (c_int, [c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_double, _P]),
-    'saicv_layernorm_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    'saicv_relu_dropout_fwd': (c_int, [c_int, _P, _P, c_size_t, c_double, ctypes.c_uint, _P, _P]),
-    'saicv_relu_dropout_bwd': (c_int, [c_int, _P, _P, _P, c_size_t, c_double, _P]),
-    'saicv_dropout_add_layernorm_fwd': (c_int, [c_int, _P, _P, c_double, ctypes.c_uint, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_double, _P]),
-    'saicv_dropout_add_layernorm_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, c_double, ctypes.c_uint, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    'saicv_layernorm_bwd_scaled': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, _P]),
-    'saicv_layernorm_bwd_ws_floats': (c_size_t, [c_int, c_int]),
-    'saicv_gelu_fwd': (c_int, [c_int, _P, _P, c_size_t, _P]),
-    'saicv_gelu_bwd': (c_int, [c_int, _P, _P, _P, c_size_t, _P]),
-    'saicv_attention_fwd': (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, _P]),
-    'saicv_attention_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, _P]),
-    'saicv_linear_gelu_fwd': (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    'saicv_linear_dgrad_gelu': (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    'saicv_linear_gelu_fwd_aux': (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    'saicv_linear_dgrad_mul': (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    'saicv_window_partition': (c_int, [c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
-    'saicv_window_unpartition': (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
-    'saicv_relpos_fwd': (c_int, [c_int, _P, c_long, c_long, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
-    'saicv_relpos_bwd': (c_int, [c_int, _P, _P, c_long, c_long, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
-    'saicv_relpos_bwd_ws_floats': (c_size_t, [c_int, c_int]),
-    'saicv_mask_loss_stats': (c_int, [c_int, _P, _P, _P, c_int, c_int, c_size_t, c_double, c_double, c_double, _P]),
-    'saicv_mask_loss_grad': (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_size_t, c_double, c_double, _P]),
-    'saicv_hyper_product_fwd': (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
-    'saicv_hyper_product_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
-    'saicv_upsample4_fwd': (c_int, [c_int, _P, _P, c_int, c_int, c_int, _P]),
-    'saicv_upsample4_bwd': (c_int, [c_int, _P, _P, c_int, c_int, c_int, _P]),
-    'saicv_mask_loss_stats_up4': (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, c_double, c_double, _P]),
-    'saicv_mask_loss_grad_up4': (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, c_double, _P]),
-    'saicv_rope_apply': (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
-    'saicv_swiglu_fwd': (c_int, [c_int, _P, _P, _P, c_size_t, _P]),
-    'saicv_swiglu_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
-    'saicv_u8_normalize': (c_int, [_P, _P, _P, _P, c_size_t, c_int, _P]),
-    'saicv_random_erase': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint, _P]),
-    'saicv_mixup_cutmix': (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
-    'saicv_soft_labels': (c_int, [_P, _P, ctypes.c_float, ctypes.c_float, _P, c_int, c_int, _P]),
-    'saicv_detr_sine_pe': (c_int, [_P, _P, c_int, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, _P]),
-    'saicv_detr_box_loss_fwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, c_double, _P, _P]),
-    'saicv_detr_box_loss_bwd': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, c_double, _P, _P]),
-    'saicv_detr_assign': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
-    'saicv_sam_prompt_tokens': (c_int, [_P, c_int, c_int, _P, _P, c_int, _P, ctypes.c_float, _P, _P, c_int, _P]),
-    'saicv_sam_prompt_tokens_bwd': (c_int, [_P, _P, _P, c_int, c_int, _P]),
-    'saicv_sam_grid_pe': (c_int, [_P, c_int, c_int, _P, _P]),
-    'saicv_dwconv2d_fwd': (c_int, [c_int, _P, _P, _P, _P] + [c_int] * 10 + [_P]),
-    'saicv_dwconv2d_dgrad': (c_int, [c_int, _P, _P, _P] + [c_int] * 10 + [_P]),
-    'saicv_dwconv2d_wgrad': (c_int, [c_int, _P, _P, _P, _P] + [c_int] * 10 + [_P]),
-    'saicv_act_fwd': (c_int, [c_int, c_int, c_double, _P, _P, c_size_t, _P]),
-    'saicv_act_bwd': (c_int, [c_int, c_int, c_double, _P, _P, _P, c_size_t, _P]),
-    'saicv_mul_fwd': (c_int, [c_int, _P, _P, _P, c_size_t, _P]),
-    'saicv_mul_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
-    'saicv_channel_scale_add_fwd': (c_int, [c_int, _P, _P, _P, _P, c_size_t, c_int, _P]),
-    'saicv_channel_scale_add_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, c_size_t, c_int, _P]),
-    'saicv_bn_stats': (c_int, [c_int, _P, c_size_t, c_int, _P, _P, _P]),
-    'saicv_resize_bilinear_add_fwd': (c_int, [c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
-    'saicv_resize_bilinear_bwd': (c_int, [c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
-    'saicv_retina_assign': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
-    'saicv_focal_loss_level': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_double, _P]),
-    'saicv_smoothl1_level': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, _P]),
-    'saicv_fcos_assign': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_double, c_int, _P]),
-    'saicv_det_best_class': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
-    'saicv_groupnorm_ws_floats': (c_size_t, [c_int, c_int]),
-    'saicv_groupnorm_fwd': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_double, c_int, _P]),
-    'saicv_groupnorm_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
-    'saicv_sam_sample_point': (c_int, [c_int, _P, _P, c_long, _P, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_uint, _P, _P,
-                                       c_int, c_int, c_int, _P]),
-    'saicv_sam_sample_point_dseed': (c_int, [c_int, _P, _P, c_long, _P, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_uint, _P, _P, _P,
-                                             c_int, c_int, c_int, _P]),
-    'saicv_comm_available': (c_int, []),
-    'saicv_comm_unique_id': (c_int, [_P]),
-    'saicv_comm_reduce_scatter': (c_int, [_P, _P, _P, c_size_t, c_int, _P]),
-    'saicv_comm_all_gather': (c_int, [_P, _P, _P, c_size_t, _P]),
-    'saicv_comm_create': (c_int, [_P, c_int, c_int, POINTER(c_void_p)]),
-    'saicv_comm_allreduce_bucket': (c_int, [_P, _P, c_size_t, c_int, _P]),
-    'saicv_comm_broadcast': (c_int, [_P, _P, c_size_t, c_int, _P]),
-    'saicv_comm_join': (c_int, [_P, _P]),
-    'saicv_comm_stats': (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(ctypes.c_ulonglong), POINTER(ctypes.c_ulonglong)]),
-    'saicv_comm_destroy': (c_int, [_P]),
-    'saicv_pixel_softmax_ce_ws_floats': (c_size_t, [c_size_t]),
-    'saicv_pixel_softmax_ce_fwd': (c_int, [c_int, _P, _P, c_size_t, c_int, _P, _P, _P, _P]),
-    'saicv_pixel_softmax_ce_bwd': (c_int, [c_int, _P, _P, _P, _P, c_size_t, c_int, _P, _P]),
-    'saicv_cpfe_gather_fwd': (c_int, [c_int, _P, c_long, _P] + [c_int] * 8 + [_P]),
-    'saicv_cpfe_gather_bwd': (c_int, [c_int, _P, _P] + [c_int] * 8 + [_P]),
-    'saicv_conv3x3_c1_ws_floats': (c_size_t, [c_int] * 4),
-    'saicv_conv3x3_c1_fwd': (c_int, [c_int, _P, _P, c_long, c_long, _P, _P] + [c_int] * 5 + [_P]),
-    'saicv_conv3x3_c1_bwd': (c_int, [c_int, _P, _P, c_long, c_long] + [_P] * 6 + [c_int] * 6 + [_P]),
-    'saicv_binary_seg_stats_ws_floats': (c_size_t, [c_int, c_size_t]),
-    'saicv_binary_seg_stats_fwd': (c_int, [_P, _P, c_int, c_size_t, _P, _P, _P]),
-    'saicv_binary_seg_stats_bwd': (c_int, [_P, _P, _P, c_int, c_size_t, _P, _P]),
-    'saicv_matting_ws_floats': (c_size_t, [c_int, c_size_t]),
-    'saicv_trimap_stats_fwd': (c_int, [_P, c_long, c_long, c_long, _P, c_int, c_size_t, ctypes.c_float, _P, _P, _P]),
-    'saicv_trimap_stats_bwd': (c_int, [_P, c_long, c_long, c_long, _P, _P, c_int, c_size_t, ctypes.c_float, _P, _P]),
-    'saicv_alpha_l1_fwd': (c_int, [_P, _P, _P, c_int, c_size_t, _P, _P, _P]),
-    'saicv_alpha_l1_bwd': (c_int, [_P, _P, _P, _P, c_int, c_size_t, _P, _P]),
-    'saicv_composition_l1_fwd': (c_int, [_P, _P, _P, _P, c_int, c_size_t, _P, _P, _P]),
-    'saicv_composition_l1_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_size_t, _P, _P]),
-    'saicv_matting_fuse_fwd': (c_int, [_P, c_long, c_long, c_long, _P, c_int, c_size_t, _P, _P]),
-    'saicv_matting_fuse_bwd': (c_int, [_P, c_long, c_long, c_long, _P, c_int, c_size_t, _P, _P]),
-    'saicv_lap_level_ws_floats': (c_size_t, [c_int] * 3),
-    'saicv_lap_level_fwd': (c_int, [_P, _P, _P] + [c_int] * 4 + [POINTER(ctypes.c_float)] + [_P] * 5),
-    'saicv_lap_level_bwd': (c_int, [_P, _P, _P] + [c_int] * 4 + [POINTER(ctypes.c_float)] + [_P] * 6),
-    'saicv_group_matting_ws_floats': (c_size_t, [c_int, c_int, c_size_t]),
-    'saicv_group_matting_stats_fwd': (c_int, [c_int] + [_P] * 8 + [c_int, c_int, c_size_t, ctypes.c_float, _P, _P, _P]),
-    'saicv_group_matting_stats_bwd': (c_int, [c_int] + [_P] * 9 + [c_int, c_int, c_size_t, _P, _P, _P, _P]),
-    'saicv_lap_level0_group_fwd': (c_int, [_P, _P, _P] + [c_int] * 4 + [POINTER(ctypes.c_float)] + [_P] * 4),
-    'saicv_lap_level_group_bwd': (c_int, [_P, _P, _P] + [c_int] * 5 + [POINTER(ctypes.c_float)] + [_P] * 5 + [c_int, _P, _P]),
-    'saicv_pixel_class_terms_ws_floats': (c_size_t, [c_size_t]),
-    'saicv_pixel_class_terms_lane_max_classes': (c_int, []),
-    'saicv_pixel_class_terms_fwd': (c_int, [c_int, _P, _P, c_size_t, c_int, c_int, c_int, _P, _P, _P]),
-    'saicv_pixel_class_terms_bwd': (c_int, [c_int, _P, _P, _P, c_size_t, c_int, c_int, c_int, _P, _P]),
-    'saicv_ctc_ws_floats': (c_size_t, [c_int, c_int, c_int]),
-    'saicv_ctc_loss_fwd': (c_int, [c_int, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P, c_int, c_int, c_int, c_int, c_int,
-                                   c_int, c_float, _P, _P, _P, _P]),
-    'saicv_ctc_loss_bwd': (c_int, [c_int, _P, ctypes.c_longlong, ctypes.c_longlong, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P,
-                                   _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P]),
-    'saicv_ctc_greedy': (c_int, [c_int, _P, ctypes.c_longlong, ctypes.c_longlong, _P, c_int, c_int, c_int, _P, _P, _P]),
-    'saicv_univseg_chunk': (c_int, []),
-    'saicv_univseg_pair_ws_floats': (c_size_t, [c_int, c_int, c_int, c_size_t]),
-    'saicv_univseg_pair_sums': (c_int, [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_size_t, _P, _P, _P]),
-    'saicv_univseg_matched_ws_floats': (c_size_t, [c_int, c_size_t]),
-    'saicv_univseg_matched_fwd': (c_int, [c_int, _P, _P, _P, _P, c_int, c_size_t, _P, _P, _P]),
-    'saicv_univseg_matched_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_size_t, _P, _P]),
-    'saicv_lstm_fwd': (c_int, [c_int, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    'saicv_lstm_bwd': (c_int, [c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
-    'saicv_attention_stream_fwd': (c_int, [c_int, c_int, _PA, _P]),
-    'saicv_attention_stream_bwd': (c_int, [c_int, c_int, _PA, _P]),
-}
+# A signature is written in the header and in the definition under csrc/: the compiler checks the two against each other,
+# and this table is the header as parsed -- name -> (restype, argtypes)
+_CONSTANTS, _STRUCTS, SIGNATURES = parse_header(open(HEADER_PATH).read())
+globals().update({k[len('SAICV_'):]: v for k, v in _CONSTANTS.items()})      # BF16, F32, PLAN_*, ROUTE_*
+globals().update({cls.__name__: cls for cls in _STRUCTS.values()})           # ConvDesc, AttnDesc, DgradFuse, PlanQuery, Plan, ...
 
 _lib = None
 

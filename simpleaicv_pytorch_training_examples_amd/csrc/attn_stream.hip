@@ -1500,8 +1500,8 @@ int sa_dispatch(int D, const SAParams& p, int which, hipStream_t st) {
 
 namespace saicv {
 
-int attention_stream(int dtype, int D, int which, const void* desc_ptr, hipStream_t st) {
-    const SAParams& p = *reinterpret_cast<const SAParams*>(desc_ptr);
+// which = 0 forward, 1 dQ pass, 2 dK/dV pass
+static int attention_stream(int dtype, int D, int which, const SAParams& p, hipStream_t st) {
     SAICV_REQUIRE(D == 32 || D == 64, "attention_stream: head dim %d (32 or 64)", D);
     SAICV_REQUIRE(p.B >= 1 && p.H >= 1 && p.Nq >= 1 && p.Nk >= 1, "attention_stream: empty problem");
     const int e = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
@@ -1536,6 +1536,21 @@ int attention_stream(int dtype, int D, int which, const void* desc_ptr, hipStrea
     }
     if (dtype == SAICV_DTYPE_BF16) return sa_dispatch<bf16_t>(D, p, which, st);
     return sa_dispatch<float>(D, p, which, st);
+}
+
+extern "C" int saicv_attention_stream_fwd(int dtype, int D, const saicv_attn_desc* desc, void* stream) {
+    SAICV_REQUIRE(desc != nullptr, "attention_stream: null descriptor");
+    return attention_stream(dtype, D, 0, *desc, S(stream));
+}
+
+extern "C" int saicv_attention_stream_bwd(int dtype, int D, const saicv_attn_desc* desc, void* stream) {
+    SAICV_REQUIRE(desc != nullptr, "attention_stream: null descriptor");
+    SAICV_REQUIRE(desc->dout && desc->dq && desc->dk && desc->dv && desc->dsum,
+                  "attention_stream_bwd: dout / dq / dk / dv / dsum are required");
+    SAICV_REQUIRE(!desc->rel_h || (desc->d_rel_h && desc->d_rel_w),
+                  "attention_stream_bwd: d_rel_h / d_rel_w are required with rel_h / rel_w");
+    const int rc = attention_stream(dtype, D, 1, *desc, S(stream));
+    return rc ? rc : attention_stream(dtype, D, 2, *desc, S(stream));
 }
 
 }  // namespace saicv

@@ -15,6 +15,7 @@
 // These kernels are HBM-bound: algorithmic bytes are listed in DESIGN.md.
 #include "common.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 
 namespace {
 
@@ -471,12 +472,13 @@ int reduce_partials(const float*& a, const float*& b, int P, int C, float* ws, h
 namespace saicv {
 
 // workspace floats needed by bn_finalize (two [32][C] slabs)
-size_t bn_ws_floats(int C) { return (size_t)64 * C; }
+extern "C" size_t saicv_bn_ws_floats(int C) { return (size_t)64 * C; }
 
-int bn_finalize_fwd(const float* sum, const float* sq, int P, int C, double count, const float* gamma,
-                    const float* beta, float* running_mean, float* running_var, double momentum,
-                    double eps, float* mean, float* invstd, float* scale, float* shift, float* ws,
-                    long long* num_batches_tracked, hipStream_t st) {
+extern "C" int saicv_bn_finalize_fwd(const float* sum, const float* sq, int P, int C, double count, const float* gamma,
+                                     const float* beta, float* running_mean, float* running_var, double momentum,
+                                     double eps, float* mean, float* invstd, float* scale, float* shift, float* ws,
+                                     long long* num_batches_tracked, void* stream) {
+    hipStream_t st = S(stream);
     P = reduce_partials(sum, sq, P, C, ws, st);
     hipLaunchKernelGGL(P <= 32 ? bn_finalize_fwd_kernel<4> : bn_finalize_fwd_kernel<16>, dim3((C + 63) / 64), dim3(P <= 32 ? 256 : 1024), 0, st, sum, sq, P, C,
                        (float)count, gamma, beta, running_mean, running_var, (float)momentum, (float)eps,
@@ -484,8 +486,9 @@ int bn_finalize_fwd(const float* sum, const float* sq, int P, int C, double coun
     return check_launch("bn_finalize_fwd");
 }
 
-int bn_eval_coeffs(int C, const float* gamma, const float* beta, const float* running_mean,
-                   const float* running_var, double eps, float* scale, float* shift, hipStream_t st) {
+extern "C" int saicv_bn_eval_coeffs(int C, const float* gamma, const float* beta, const float* running_mean,
+                                    const float* running_var, double eps, float* scale, float* shift, void* stream) {
+    hipStream_t st = S(stream);
     hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3((C + 63) / 64), dim3(64), 0, st, C, gamma, beta,
                        running_mean, running_var, (float)eps, scale, shift);
     return check_launch("bn_eval_coeffs");
@@ -513,8 +516,9 @@ static int bn_act_fwd_t(const void* y, const void* res, void* z, const float* sc
     return check_launch("bn_act_fwd");
 }
 
-int bn_act_fwd(int dtype, const void* y, const void* res, void* z, const float* scale,
-               const float* shift, size_t M, int C, int relu, void* relu_mask, hipStream_t st) {
+extern "C" int saicv_bn_act_fwd(int dtype, const void* y, const void* res, void* z, const float* scale,
+                                const float* shift, size_t M, int C, int relu, void* relu_mask, void* stream) {
+    hipStream_t st = S(stream);
     uint8_t* mask = (uint8_t*)relu_mask;
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0, "bn_act_fwd: C=%d must be a multiple of %d", C, n);
@@ -522,10 +526,11 @@ int bn_act_fwd(int dtype, const void* y, const void* res, void* z, const float* 
     return bn_act_fwd_t<float>(y, res, z, scale, shift, M, C, relu, mask, st);
 }
 
-int bn_act_fwd_stats(int dtype, const void* y, const void* res, void* z, const float* sum, const float* sq, int rows,
-                     double count, const float* gamma, const float* beta, float* running_mean, float* running_var,
-                     double momentum, double eps, long long* num_batches_tracked, float* mean_out, float* invstd_out, size_t M,
-                     int C, int relu, void* relu_mask, hipStream_t st) {
+extern "C" int saicv_bn_act_fwd_stats(int dtype, const void* y, const void* res, void* z, const float* sum, const float* sq, int rows,
+                                      double count, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                      double momentum, double eps, long long* num_batches_tracked, float* mean_out, float* invstd_out, size_t M,
+                                      int C, int relu, void* relu_mask, void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0 && C <= kInlineMaxC, "bn_act_fwd_stats: C=%d must be a multiple of %d and <= %d", C, n, kInlineMaxC);
     SAICV_REQUIRE(sum && sq && rows >= 1 && rows <= 64 && mean_out && invstd_out, "bn_act_fwd_stats: statistics rows / outputs missing");
@@ -538,11 +543,12 @@ int bn_act_fwd_stats(int dtype, const void* y, const void* res, void* z, const f
 // the residual join of a block whose shortcut is a convolution + BatchNorm (downsample): that BatchNorm's apply happens in this
 // pass (res_scale / res_shift), its output is never written.  sum != NULL: the main branch's statistics arrive as atomically
 // accumulated rows (as bn_act_fwd_stats), else scale / shift are given (as bn_act_fwd).
-int bn_act_fwd_join(int dtype, const void* y, const void* res, const float* res_scale, const float* res_shift, void* z,
-                    const float* scale, const float* shift, const float* sum, const float* sq, int rows, double count,
-                    const float* gamma, const float* beta, float* running_mean, float* running_var, double momentum, double eps,
-                    long long* num_batches_tracked, float* mean_out, float* invstd_out, size_t M, int C, int relu, void* relu_mask,
-                    hipStream_t st) {
+extern "C" int saicv_bn_act_fwd_join(int dtype, const void* y, const void* res, const float* res_scale, const float* res_shift, void* z,
+                                     const float* scale, const float* shift, const float* sum, const float* sq, int rows, double count,
+                                     const float* gamma, const float* beta, float* running_mean, float* running_var, double momentum, double eps,
+                                     long long* num_batches_tracked, float* mean_out, float* invstd_out, size_t M, int C, int relu, void* relu_mask,
+                                     void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0 && C % 4 == 0, "bn_act_fwd_join: C=%d must be a multiple of %d", C, n);
     SAICV_REQUIRE(res && res_scale && res_shift, "bn_act_fwd_join: residual and its coefficients are required");
@@ -572,7 +578,7 @@ int bn_bwd_slabs(size_t M, int C, int dtype) {
 }
 
 // workspace: [2][slabs][C] partials + [2][32][C] second stage + 3*C coefficients
-size_t bn_bwd_ws_floats(size_t M, int C, int dtype) {
+extern "C" size_t saicv_bn_bwd_ws_floats(size_t M, int C, int dtype) {
     return (size_t)2 * bn_bwd_slabs(M, C, dtype) * C + (size_t)64 * C + (size_t)3 * C;
 }
 
@@ -633,9 +639,10 @@ static int bn_bwd_inline_t(const void* dz, const uint8_t* mask, const void* y, v
 }
 
 // backward with the reduction already done into a few atomically accumulated rows: ONE launch (coefficients in-kernel)
-int bn_bwd_inline(int dtype, const void* dz, const void* relu_mask, const void* y, const float* gamma, const float* mean,
-                  const float* invstd, const float* part_g, const float* part_gx, int rows, void* dy, void* dres, float* dgamma,
-                  float* dbeta, size_t M, int C, int relu, int accumulate, hipStream_t st) {
+extern "C" int saicv_bn_act_bwd_inline(int dtype, const void* dz, const void* relu_mask, const void* y, const float* gamma, const float* mean,
+                                       const float* invstd, const float* part_g, const float* part_gx, int rows, void* dy, void* dres, float* dgamma,
+                                       float* dbeta, size_t M, int C, int relu, int accumulate, void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0 && C <= kInlineMaxC, "bn_bwd_inline: C=%d must be a multiple of %d and <= %d", C, n, kInlineMaxC);
     SAICV_REQUIRE(part_g && part_gx && rows >= 1 && rows <= 64, "bn_bwd_inline: partial sums missing");
@@ -645,10 +652,11 @@ int bn_bwd_inline(int dtype, const void* dz, const void* relu_mask, const void* 
     return bn_bwd_inline_t<float>(dz, (const uint8_t*)relu_mask, y, dy, dres, M, C, relu, inl, st);
 }
 
-int bn_bwd_from_partials(int dtype, const void* dz, const void* relu_mask, const void* y, const float* gamma,
-                         const float* mean, const float* invstd, const float* part_g, const float* part_gx, int rows,
-                         void* dy, void* dres, float* dgamma, float* dbeta, size_t M, int C, int relu, int accumulate,
-                         float* ws, hipStream_t st) {
+extern "C" int saicv_bn_act_bwd_from_partials(int dtype, const void* dz, const void* relu_mask, const void* y, const float* gamma,
+                                              const float* mean, const float* invstd, const float* part_g, const float* part_gx, int rows,
+                                              void* dy, void* dres, float* dgamma, float* dbeta, size_t M, int C, int relu, int accumulate,
+                                              float* ws, void* stream) {
+    hipStream_t st = S(stream);
     const uint8_t* mask = (const uint8_t*)relu_mask;
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0, "bn_bwd_from_partials: C=%d must be a multiple of %d", C, n);
@@ -674,9 +682,10 @@ int bn_bwd_coeffs(const float* part_g, const float* part_gx, int rows, int C, si
     return check_launch("bn_bwd_coeffs");
 }
 
-int bn_bwd(int dtype, const void* dz, const void* z, const void* relu_mask, const void* y, const float* gamma,
-           const float* mean, const float* invstd, void* dy, void* dres, float* dgamma, float* dbeta,
-           size_t M, int C, int relu, int accumulate, float* ws, hipStream_t st) {
+extern "C" int saicv_bn_act_bwd(int dtype, const void* dz, const void* z, const void* relu_mask, const void* y, const float* gamma,
+                                const float* mean, const float* invstd, void* dy, void* dres, float* dgamma, float* dbeta,
+                                size_t M, int C, int relu, int accumulate, float* ws, void* stream) {
+    hipStream_t st = S(stream);
     const uint8_t* mask = (const uint8_t*)relu_mask;
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0, "bn_bwd: C=%d must be a multiple of %d", C, n);

@@ -382,7 +382,7 @@ namespace saicv {
 
 // Rows of partial BatchNorm-backward sums of the launch for a shape it has a form for (no switches), else 0.  Buffer-addressed operands stay below 4 GiB,
 // the last tile's rows past M included.
-int c3_bwd_stream_rows(int M, int CO, int CI) {
+extern "C" int saicv_c3_bwd_stream_rows(int M, int CO, int CI) {
     if (M < 1 || ((size_t)M + kTilePx) * CO * 2 >= 0xfffffff0ull) return 0;
     for (const C3Shape& s : kC3Shapes)
         if (s.co == CO && s.ci == CI) return c3_sum_rows(M, CI);
@@ -408,32 +408,32 @@ static int c3_plan(int M, int CO, int CI, int* splits, int* tiles_per_wg) {
 // weight-gradient parts.  (The fast mode of the kernels this launch replaces adds the splits' tiles with fp32 atomics in completion
 // order; here the parts are parked and folded in BOTH modes -- the fold is 5 us at 56 x 56, and the sum of 245 ... 256 atomics in
 // an order that changes from run to run strayed up to 2.4 times as far from float64 as the three kernels' did.)
-size_t c3_bwd_stream_ws_floats(int M, int CO, int CI) {
+extern "C" size_t saicv_c3_bwd_stream_ws_floats(int M, int CO, int CI) {
     size_t n = (size_t)67 * CO;
     int splits = 0, tpw = 0;
-    if (!g_deterministic && c3_bwd_stream_rows(M, CO, CI) > 0 && c3_plan(M, CO, CI, &splits, &tpw) == 0 && splits > 1)
+    if (!g_deterministic && saicv_c3_bwd_stream_rows(M, CO, CI) > 0 && c3_plan(M, CO, CI, &splits, &tpw) == 0 && splits > 1)
         n += (size_t)splits * CO * CI;
     return n;
 }
 
 // Rows of partial BatchNorm-backward sums of the fused launch, 0 if the three-kernel route keeps this layer.  A pure
 // function of its arguments and of SAICV_C3_BWD_STREAM (default 1) / SAICV_C3_BWD_MIN_ROWS (default 65536), read per call.
-int c3_bwd_stream_blocks(int dtype, int M, int CO, int CI) {
+extern "C" int saicv_c3_bwd_stream_ok(int dtype, int M, int CO, int CI) {
     const char* es = getenv("SAICV_C3_BWD_STREAM");
     const char* er = getenv("SAICV_C3_BWD_MIN_ROWS");
     const int on = es ? atoi(es) : 1;
     const int min_rows = er ? atoi(er) : 65536;
     if (!on || dtype != SAICV_DTYPE_BF16 || M < min_rows) return 0;
     for (const C3Shape& s : kC3Shapes)
-        if (s.co == CO && s.ci == CI && s.routed) return c3_bwd_stream_rows(M, CO, CI);
+        if (s.co == CO && s.ci == CI && s.routed) return saicv_c3_bwd_stream_rows(M, CO, CI);
     return 0;
 }
 
 // The launch (no switches: any M).  coef = [3][CO] as bn_finalize_bwd_kernel wrote them; ex: the bs_* operands of EpiExtra or nullptr;
-// bs_rows > 0: the sums are added into that many pooled rows, else c3_bwd_stream_rows() rows are written.
+// bs_rows > 0: the sums are added into that many pooled rows, else saicv_c3_bwd_stream_rows() rows are written.
 int c3_bwd_stream(int M, int CO, int CI, const void* dz, const void* y, const void* mask, const float* coef, const void* x,
                   const void* wd, void* dx, float* dw, const EpiExtra* ex, int bs_rows, float* part_ws, hipStream_t st) {
-    SAICV_REQUIRE(c3_bwd_stream_rows(M, CO, CI) > 0, "c3_bwd_stream: no form for M = %d, Cout = %d, Cin = %d (bf16, (256, 64) or (512, 128), "
+    SAICV_REQUIRE(saicv_c3_bwd_stream_rows(M, CO, CI) > 0, "c3_bwd_stream: no form for M = %d, Cout = %d, Cin = %d (bf16, (256, 64) or (512, 128), "
                   "operands below 4 GiB)", M, CO, CI);
     SAICV_REQUIRE(dz && y && mask && coef && x && wd && dx && dw, "c3_bwd_stream: operand missing");
     C3Params p = {};

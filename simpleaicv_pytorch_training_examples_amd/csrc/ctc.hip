@@ -38,6 +38,7 @@
 #include "common.h"
 #include "ordered_sum.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 
 namespace {
 
@@ -449,7 +450,7 @@ namespace saicv {
 
 // floats of workspace for ctc_loss_fwd; the pieces, in order: lse [T B 4] (row maximum, log of the rescaled sum, that sum less 1, arg-max), lp [T B W], occ [T B W], alpha [B T (2 S + 1)],
 // slotcls [B W] (int32), feas [B], term [B]   (W = 1 + S)
-size_t ctc_ws_floats(int Tn, int B, int S) {
+extern "C" size_t saicv_ctc_ws_floats(int Tn, int B, int S) {
     const size_t rows = (size_t)Tn * B, W = 1 + (size_t)S;
     return 4 * rows + 2 * rows * W + rows * (2 * (size_t)S + 1) + (size_t)B * W + 2 * (size_t)B;
 }
@@ -473,8 +474,9 @@ CtcWs ctc_carve(float* ws, int Tn, int B, int S) {
 }
 }  // namespace
 
-int ctc_loss_fwd(int dtype, const void* logits, long long st, long long sb, const int* targets, const int* in_len, const int* tg_len,
-                 int Tn, int B, int S, int C, int blank, int focal, float gamma, float* ws, float* nll, float* loss, hipStream_t s) {
+extern "C" int saicv_ctc_loss_fwd(int dtype, const void* logits, long long st, long long sb, const int* targets, const int* in_len, const int* tg_len,
+                                  int Tn, int B, int S, int C, int blank, int focal, float gamma, float* ws, float* nll, float* loss, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (ctc_check("ctc_loss_fwd", logits, Tn, B, C, st, sb)) return -1;
     SAICV_REQUIRE(targets && in_len && tg_len && ws && nll && loss, "ctc_loss_fwd: null targets, lengths, workspace or output");
     SAICV_REQUIRE(S >= 1 && S <= CTC_MAX_S, "ctc_loss_fwd: targets are [B, %d]; 1 .. %d columns", S, CTC_MAX_S);
@@ -498,9 +500,10 @@ int ctc_loss_fwd(int dtype, const void* logits, long long st, long long sb, cons
     return check_launch("ctc_loss_fwd");
 }
 
-int ctc_loss_bwd(int dtype, const void* logits, long long st, long long sb, void* dlogits, long long dst, long long dsb,
-                 const int* in_len, const int* tg_len, const float* ws, const float* nll, const float* gout, int Tn, int B, int S, int C,
-                 int focal, float gamma, hipStream_t s) {
+extern "C" int saicv_ctc_loss_bwd(int dtype, const void* logits, long long st, long long sb, void* dlogits, long long dst, long long dsb,
+                                  const int* in_len, const int* tg_len, const float* ws, const float* nll, const float* gout, int Tn, int B, int S, int C,
+                                  int focal, float gamma, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (ctc_check("ctc_loss_bwd", logits, Tn, B, C, st, sb)) return -1;
     SAICV_REQUIRE(dlogits && in_len && tg_len && ws && nll && gout, "ctc_loss_bwd: null gradient, lengths, workspace or dL/dloss");
     SAICV_REQUIRE(S >= 1 && S <= CTC_MAX_S, "ctc_loss_bwd: targets are [B, %d]; 1 .. %d columns", S, CTC_MAX_S);
@@ -519,8 +522,9 @@ int ctc_loss_bwd(int dtype, const void* logits, long long st, long long sb, void
     return check_launch("ctc_loss_bwd");
 }
 
-int ctc_greedy(int dtype, const void* logits, long long st, long long sb, const int* in_len, int Tn, int B, int C, int* index,
-               float* prob, hipStream_t s) {
+extern "C" int saicv_ctc_greedy(int dtype, const void* logits, long long st, long long sb, const int* in_len, int Tn, int B, int C, int* index,
+                                float* prob, void* stream) {
+    hipStream_t s = S(stream);
     if (ctc_check("ctc_greedy", logits, Tn, B, C, st, sb)) return -1;
     SAICV_REQUIRE(index && prob, "ctc_greedy: null output");
     const int blocks = (int)(((long long)Tn * B + 3) / 4);

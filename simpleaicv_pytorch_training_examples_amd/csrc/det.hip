@@ -3,6 +3,7 @@
 
 #include "common.h"
 #include "det.h"
+#include "../../include/saicv_hip.h"
 
 namespace saicv {
 

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "saicv_internal.h"
 #include "det.h"
+#include "../../include/saicv_hip.h"
 
 namespace {
 

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "ordered_sum.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 
 namespace {
 
@@ -92,8 +93,9 @@ __global__ __launch_bounds__(256) void scale_by_scalar_kernel(const float* __res
 
 namespace saicv {
 
-int softmax_ce_fwd(const float* logits, const void* label, int soft, int B, int C, float* row_loss,
-                   float* loss, float* dlogits, hipStream_t st) {
+extern "C" int saicv_softmax_ce_fwd(const float* logits, const void* label, int soft, int B, int C, float* row_loss,
+                                    float* loss, float* dlogits, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(B > 0 && C > 0, "softmax_ce_fwd: empty problem");
     const int grid = (B + 3) / 4;
     if (soft)
@@ -104,8 +106,9 @@ int softmax_ce_fwd(const float* logits, const void* label, int soft, int B, int 
     return check_launch("softmax_ce_fwd");
 }
 
-int scale_by_scalar(int out_dtype, const float* in, const float* scale, void* out, size_t n,
-                    hipStream_t st) {
+extern "C" int saicv_scale_by_scalar(int out_dtype, const float* in, const float* scale, void* out, size_t n,
+                                     void* stream) {
+    hipStream_t st = S(stream);
     size_t b = (n + 255) / 256;
     if (b > 2048) b = 2048;
     if (b < 1) b = 1;

@@ -11,6 +11,7 @@
 // copy it makes once per call.  The A operand (h_{t-1}, 16 x H; dgates_t, 16 x 4H) sits in LDS.
 #include "common.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 
 namespace saicv {
 namespace {
@@ -270,7 +271,8 @@ void lstm_allow_lds(K k) {
 }
 }  // namespace
 
-int lstm_fwd(int dtype, float* gates, const void* whh, void* y, float* c, int B, int Tn, int H, hipStream_t s) {
+extern "C" int saicv_lstm_fwd(int dtype, float* gates, const void* whh, void* y, float* c, int B, int Tn, int H, void* stream) {
+    hipStream_t s = S(stream);
     if (lstm_check("lstm_fwd", dtype, B, Tn, H)) return -1;
     SAICV_REQUIRE(gates && whh && y && c, "lstm_fwd: null gates, weights, output or cell state");
     const size_t esz = dtype == SAICV_DTYPE_BF16 ? 2 : 4;
@@ -297,8 +299,9 @@ int lstm_fwd(int dtype, float* gates, const void* whh, void* y, float* c, int B,
     return check_launch("lstm_fwd");
 }
 
-int lstm_bwd(int dtype, const void* dy, const float* acts, const float* c, const void* whhT, void* dgates, int B, int Tn, int H,
-             hipStream_t s) {
+extern "C" int saicv_lstm_bwd(int dtype, const void* dy, const float* acts, const float* c, const void* whhT, void* dgates, int B, int Tn, int H,
+                              void* stream) {
+    hipStream_t s = S(stream);
     if (lstm_check("lstm_bwd", dtype, B, Tn, H)) return -1;
     SAICV_REQUIRE(dy && acts && c && whhT && dgates, "lstm_bwd: null gradient, saved state, weights or output");
     const size_t esz = dtype == SAICV_DTYPE_BF16 ? 2 : 4;

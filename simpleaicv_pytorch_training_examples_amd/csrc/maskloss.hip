@@ -12,6 +12,7 @@
 // HBM-bound: algorithmic bytes = logits + targets read once (forward), + d logits written (backward).
 #include "common.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 #include "det.h"
 #include "maskterm.h"
 #include "ordered_sum.h"
@@ -112,8 +113,9 @@ __global__ __launch_bounds__(ML_THREADS) void mask_loss_grad_kernel(const T* __r
 
 namespace saicv {
 
-int mask_loss_stats(int dtype, const void* logits, const float* targets, float* stats, int B, int M, size_t HW,
-                    double alpha, double gamma, double thr, hipStream_t st) {
+extern "C" int saicv_mask_loss_stats(int dtype, const void* logits, const float* targets, float* stats, int B, int M, size_t HW,
+                                     double alpha, double gamma, double thr, void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(B > 0 && M > 0 && HW > 0 && HW % n == 0, "mask_loss_stats: H*W=%zu must be a positive multiple of %d", HW, n);
     hipMemsetAsync(stats, 0, (size_t)B * M * 6 * sizeof(float), st);
@@ -131,8 +133,9 @@ int mask_loss_stats(int dtype, const void* logits, const float* targets, float* 
     return det.fold(stats, 0, (size_t)B * M * 6);
 }
 
-int mask_loss_grad(int dtype, const void* logits, const float* targets, const float* coef, void* dlogits, int B, int M,
-                   size_t HW, double alpha, double gamma, hipStream_t st) {
+extern "C" int saicv_mask_loss_grad(int dtype, const void* logits, const float* targets, const float* coef, void* dlogits, int B, int M,
+                                    size_t HW, double alpha, double gamma, void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(B > 0 && M > 0 && HW > 0 && HW % n == 0, "mask_loss_grad: H*W=%zu must be a positive multiple of %d", HW, n);
     const size_t per_block = (size_t)ML_THREADS * ML_CHUNKS * n;

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "ordered_sum.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 
 namespace {
 
@@ -797,13 +798,14 @@ int lap_tiles(const LapGeom& g) { return g.tiles_x * ((g.h + LP_T - 1) / LP_T); 
 
 namespace saicv {
 
-size_t matting_ws_floats(int B, size_t P) {
+extern "C" size_t saicv_matting_ws_floats(int B, size_t P) {
     if (B <= 0 || P == 0) return 0;
     return (size_t)B * ((P + MT_SPAN - 1) / MT_SPAN) * 2;
 }
 
-int trimap_stats_fwd(const float* gp, long sb, long sc, long sp, const float* trimap, int B, size_t P, float smooth, float* partial,
-                     float* stats, hipStream_t st) {
+extern "C" int saicv_trimap_stats_fwd(const float* gp, long sb, long sc, long sp, const float* trimap, int B, size_t P, float smooth, float* partial,
+                                      float* stats, void* stream) {
+    hipStream_t st = S(stream);
     Tri t;
     if (tri_make(t, "trimap_stats_fwd", gp, sb, sc, sp, B, P, smooth)) return -1;
     SAICV_REQUIRE(trimap != nullptr && partial != nullptr && stats != nullptr, "trimap_stats_fwd: null trimap, workspace or output");
@@ -814,8 +816,9 @@ int trimap_stats_fwd(const float* gp, long sb, long sc, long sp, const float* tr
     return check_launch("trimap_stats_fwd");
 }
 
-int trimap_stats_bwd(const float* gp, long sb, long sc, long sp, const float* trimap, const float* gstats, int B, size_t P,
-                     float smooth, float* dgp, hipStream_t st) {
+extern "C" int saicv_trimap_stats_bwd(const float* gp, long sb, long sc, long sp, const float* trimap, const float* gstats, int B, size_t P,
+                                      float smooth, float* dgp, void* stream) {
+    hipStream_t st = S(stream);
     Tri t;
     if (tri_make(t, "trimap_stats_bwd", gp, sb, sc, sp, B, P, smooth)) return -1;
     SAICV_REQUIRE(trimap != nullptr && gstats != nullptr && dgp != nullptr, "trimap_stats_bwd: null trimap or gradient");
@@ -824,8 +827,9 @@ int trimap_stats_bwd(const float* gp, long sb, long sc, long sp, const float* tr
     return check_launch("trimap_stats_bwd");
 }
 
-int alpha_l1_fwd(const float* pred, const float* alpha, const float* trimap, int B, size_t P, float* partial, float* sums,
-                 hipStream_t st) {
+extern "C" int saicv_alpha_l1_fwd(const float* pred, const float* alpha, const float* trimap, int B, size_t P, float* partial, float* sums,
+                                  void* stream) {
+    hipStream_t st = S(stream);
     if (mt_check("alpha_l1_fwd", B, P)) return -1;
     SAICV_REQUIRE(pred != nullptr && alpha != nullptr && partial != nullptr && sums != nullptr, "alpha_l1_fwd: null argument");
     const int vec = P % 4 == 0 && mt_al16(pred) && mt_al16(alpha) && mt_al16(trimap);
@@ -835,8 +839,9 @@ int alpha_l1_fwd(const float* pred, const float* alpha, const float* trimap, int
     return check_launch("alpha_l1_fwd");
 }
 
-int alpha_l1_bwd(const float* pred, const float* alpha, const float* trimap, const float* gsums, int B, size_t P, float* dpred,
-                 hipStream_t st) {
+extern "C" int saicv_alpha_l1_bwd(const float* pred, const float* alpha, const float* trimap, const float* gsums, int B, size_t P, float* dpred,
+                                  void* stream) {
+    hipStream_t st = S(stream);
     if (mt_check("alpha_l1_bwd", B, P)) return -1;
     SAICV_REQUIRE(pred != nullptr && alpha != nullptr && gsums != nullptr && dpred != nullptr, "alpha_l1_bwd: null argument");
     const int vec = P % 4 == 0 && mt_al16(pred) && mt_al16(alpha) && mt_al16(trimap) && mt_al16(dpred);
@@ -844,8 +849,9 @@ int alpha_l1_bwd(const float* pred, const float* alpha, const float* trimap, con
     return check_launch("alpha_l1_bwd");
 }
 
-int composition_l1_fwd(const float* pred, const float* fg, const float* bg, const float* image, int B, size_t P, float* partial,
-                       float* sums, hipStream_t st) {
+extern "C" int saicv_composition_l1_fwd(const float* pred, const float* fg, const float* bg, const float* image, int B, size_t P, float* partial,
+                                        float* sums, void* stream) {
+    hipStream_t st = S(stream);
     if (mt_check("composition_l1_fwd", B, P)) return -1;
     SAICV_REQUIRE(pred && fg && bg && image && partial && sums, "composition_l1_fwd: null argument");
     const int vec = P % 4 == 0 && mt_al16(pred) && mt_al16(fg) && mt_al16(bg) && mt_al16(image);
@@ -856,8 +862,9 @@ int composition_l1_fwd(const float* pred, const float* fg, const float* bg, cons
     return check_launch("composition_l1_fwd");
 }
 
-int composition_l1_bwd(const float* pred, const float* fg, const float* bg, const float* image, const float* gsums, int B, size_t P,
-                       float* dpred, hipStream_t st) {
+extern "C" int saicv_composition_l1_bwd(const float* pred, const float* fg, const float* bg, const float* image, const float* gsums, int B, size_t P,
+                                        float* dpred, void* stream) {
+    hipStream_t st = S(stream);
     if (mt_check("composition_l1_bwd", B, P)) return -1;
     SAICV_REQUIRE(pred && fg && bg && image && gsums && dpred, "composition_l1_bwd: null argument");
     const int vec = P % 4 == 0 && mt_al16(pred) && mt_al16(fg) && mt_al16(bg) && mt_al16(image) && mt_al16(dpred);
@@ -865,7 +872,8 @@ int composition_l1_bwd(const float* pred, const float* fg, const float* bg, cons
     return check_launch("composition_l1_bwd");
 }
 
-int matting_fuse_fwd(const float* gp, long sb, long sc, long sp, const float* local, int B, size_t P, float* fused, hipStream_t st) {
+extern "C" int saicv_matting_fuse_fwd(const float* gp, long sb, long sc, long sp, const float* local, int B, size_t P, float* fused, void* stream) {
+    hipStream_t st = S(stream);
     Tri t;
     if (tri_make(t, "matting_fuse_fwd", gp, sb, sc, sp, B, P, 0.f)) return -1;
     SAICV_REQUIRE(local != nullptr && fused != nullptr, "matting_fuse_fwd: null local prediction or output");
@@ -874,7 +882,8 @@ int matting_fuse_fwd(const float* gp, long sb, long sc, long sp, const float* lo
     return check_launch("matting_fuse_fwd");
 }
 
-int matting_fuse_bwd(const float* gp, long sb, long sc, long sp, const float* dfused, int B, size_t P, float* dlocal, hipStream_t st) {
+extern "C" int saicv_matting_fuse_bwd(const float* gp, long sb, long sc, long sp, const float* dfused, int B, size_t P, float* dlocal, void* stream) {
+    hipStream_t st = S(stream);
     Tri t;
     if (tri_make(t, "matting_fuse_bwd", gp, sb, sc, sp, B, P, 0.f)) return -1;
     SAICV_REQUIRE(dfused != nullptr && dlocal != nullptr, "matting_fuse_bwd: null gradient");
@@ -883,7 +892,7 @@ int matting_fuse_bwd(const float* gp, long sb, long sc, long sp, const float* df
     return check_launch("matting_fuse_bwd");
 }
 
-size_t group_matting_ws_floats(int B, int M, size_t P) {
+extern "C" size_t saicv_group_matting_ws_floats(int B, int M, size_t P) {
     if (B <= 0 || M <= 0 || P == 0) return 0;
     return (size_t)B * ((M + GM_M - 1) / GM_M) * ((P + MT_SPAN - 1) / MT_SPAN) * (GM_M * GM_K);
 }
@@ -899,9 +908,10 @@ int gm_check(const char* what, int dtype, const void* gp, const void* lp, const 
 }
 }  // namespace
 
-int group_matting_stats_fwd(int dtype, const void* gp, const void* lp, const void* fp, const float* alpha, const float* trimap,
-                            const float* image, const float* fg, const float* bg, int B, int M, size_t P, float thr, float* partial,
-                            float* stats, hipStream_t st) {
+extern "C" int saicv_group_matting_stats_fwd(int dtype, const void* gp, const void* lp, const void* fp, const float* alpha, const float* trimap,
+                                             const float* image, const float* fg, const float* bg, int B, int M, size_t P, float thr, float* partial,
+                                             float* stats, void* stream) {
+    hipStream_t st = S(stream);
     if (gm_check("group_matting_stats_fwd", dtype, gp, lp, fp, alpha, trimap, image, fg, bg, B, M, P)) return -1;
     SAICV_REQUIRE(partial != nullptr && stats != nullptr, "group_matting_stats_fwd: null workspace or output");
     const GmTargets t = {alpha, trimap, image, fg, bg};
@@ -919,9 +929,10 @@ int group_matting_stats_fwd(int dtype, const void* gp, const void* lp, const voi
     return check_launch("group_matting_stats_fwd");
 }
 
-int group_matting_stats_bwd(int dtype, const void* gp, const void* lp, const void* fp, const float* alpha, const float* trimap,
-                            const float* image, const float* fg, const float* bg, const float* gstats, int B, int M, size_t P,
-                            void* dgp, void* dlp, void* dfp, hipStream_t st) {
+extern "C" int saicv_group_matting_stats_bwd(int dtype, const void* gp, const void* lp, const void* fp, const float* alpha, const float* trimap,
+                                             const float* image, const float* fg, const float* bg, const float* gstats, int B, int M, size_t P,
+                                             void* dgp, void* dlp, void* dfp, void* stream) {
+    hipStream_t st = S(stream);
     if (gm_check("group_matting_stats_bwd", dtype, gp, lp, fp, alpha, trimap, image, fg, bg, B, M, P)) return -1;
     SAICV_REQUIRE(gstats && dgp && dlp && dfp, "group_matting_stats_bwd: null gradient");
     const GmTargets t = {alpha, trimap, image, fg, bg};
@@ -937,13 +948,15 @@ int group_matting_stats_bwd(int dtype, const void* gp, const void* lp, const voi
     return check_launch("group_matting_stats_bwd");
 }
 
-size_t lap_level_ws_floats(int B, int h, int w) {
+extern "C" size_t saicv_lap_level_ws_floats(int B, int h, int w) {
     if (B <= 0 || h <= 0 || w <= 0) return 0;
     return (size_t)B * ((h + LP_T - 1) / LP_T) * ((w + LP_T - 1) / LP_T) * 2;
 }
 
-int lap_level_fwd(const float* src, const float* alpha, const float* trimap, int level0, int B, int h, int w, const float* table,
-                  float* next, float* partial, float* sum_e, float* sum_next, hipStream_t st) {
+extern "C" int saicv_lap_level_fwd(const float* src, const float* alpha, const float* trimap, int level0, int B, int h, int w,
+                                   const float* table, float* next, float* partial, float* sum_e, float* sum_next, void* stream) {
+    SAICV_REQUIRE(table != nullptr, "lap_level_fwd: null weight table");
+    hipStream_t st = S(stream);
     LapGeom g;
     if (lap_geom(g, "lap_level_fwd", B, h, w, level0)) return -1;
     SAICV_REQUIRE(src != nullptr && table != nullptr && partial != nullptr && sum_e != nullptr, "lap_level_fwd: null argument");
@@ -960,8 +973,11 @@ int lap_level_fwd(const float* src, const float* alpha, const float* trimap, int
     return check_launch("lap_level_fwd");
 }
 
-int lap_level_bwd(const float* src, const float* alpha, const float* trimap, int level0, int B, int h, int w, const float* table,
-                  const float* gnext, const float* topcur, const float* gs, const float* gtop, float* gcur, hipStream_t st) {
+extern "C" int saicv_lap_level_bwd(const float* src, const float* alpha, const float* trimap, int level0, int B, int h, int w,
+                                   const float* table, const float* gnext, const float* topcur, const float* gs, const float* gtop,
+                                   float* gcur, void* stream) {
+    SAICV_REQUIRE(table != nullptr, "lap_level_bwd: null weight table");
+    hipStream_t st = S(stream);
     LapGeom g;
     if (lap_geom(g, "lap_level_bwd", B, h, w, level0)) return -1;
     SAICV_REQUIRE(src != nullptr && table != nullptr && gs != nullptr && gcur != nullptr, "lap_level_bwd: null argument");
@@ -975,8 +991,10 @@ int lap_level_bwd(const float* src, const float* alpha, const float* trimap, int
     return check_launch("lap_level_bwd");
 }
 
-int lap_level0_group_fwd(const float* src, const float* alpha, const float* trimap, int group, int R, int h, int w, const float* table,
-                         float* next, float* partial, float* sum_e, hipStream_t st) {
+extern "C" int saicv_lap_level0_group_fwd(const float* src, const float* alpha, const float* trimap, int group, int R, int h, int w,
+                                          const float* table, float* next, float* partial, float* sum_e, void* stream) {
+    SAICV_REQUIRE(table != nullptr, "lap_level0_group_fwd: null weight table");
+    hipStream_t st = S(stream);
     LapGeom g;
     if (lap_geom(g, "lap_level0_group_fwd", R, h, w, 1, group)) return -1;
     SAICV_REQUIRE(src && alpha && table && partial && sum_e, "lap_level0_group_fwd: null argument");
@@ -989,9 +1007,11 @@ int lap_level0_group_fwd(const float* src, const float* alpha, const float* trim
     return check_launch("lap_level0_group_fwd");
 }
 
-int lap_level_group_bwd(const float* src, const float* alpha, const float* trimap, int level0, int group, int R, int h, int w,
-                        const float* table, const float* gnext, const float* topcur, const float* gs, const float* gtop,
-                        const float* gall, int nsum, float* gcur, hipStream_t st) {
+extern "C" int saicv_lap_level_group_bwd(const float* src, const float* alpha, const float* trimap, int level0, int group, int R, int h,
+                                         int w, const float* table, const float* gnext, const float* topcur, const float* gs,
+                                         const float* gtop, const float* gall, int nsum, float* gcur, void* stream) {
+    SAICV_REQUIRE(table != nullptr, "lap_level_group_bwd: null weight table");
+    hipStream_t st = S(stream);
     LapGeom g;
     if (lap_geom(g, "lap_level_group_bwd", R, h, w, level0, level0 ? group : 1)) return -1;
     SAICV_REQUIRE(src && table && gs && gall && gcur && nsum > 0, "lap_level_group_bwd: null argument");

@@ -23,6 +23,7 @@
 // That halves the distance to float64 arithmetic at no cost; with integer operands the residuals are 0.
 #include "common.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 
 namespace {
 
@@ -319,9 +320,10 @@ __global__ __launch_bounds__(256) void muon_apply_kernel(float* __restrict__ p, 
 
 namespace saicv {
 
-int muon_prepare(float* p, const float* g, float* s1, float* s2, const int32_t* block_prob, const int32_t* tab,
-                 const float* hyper, const float* inv_scale, const float* found_inf, const uint8_t* has_grad,
-                 float* step_blk, void* xws, size_t n, hipStream_t st) {
+extern "C" int saicv_muon_prepare(float* p, const float* g, float* s1, float* s2, const int32_t* block_prob, const int32_t* tab,
+                                  const float* hyper, const float* inv_scale, const float* found_inf, const uint8_t* has_grad,
+                                  float* step_blk, void* xws, size_t n, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(n % 1024 == 0 && n > 0, "muon_prepare: arena length %zu must be a positive multiple of 1024", n);
     SAICV_REQUIRE(step_blk != nullptr && block_prob != nullptr, "muon_prepare: the per-block tables are required");
     hipLaunchKernelGGL(muon_prepare_kernel, dim3((unsigned)(n / 1024)), dim3(256), 0, st, p, g, s1, s2, block_prob, tab, hyper,
@@ -330,9 +332,10 @@ int muon_prepare(float* p, const float* g, float* s1, float* s2, const int32_t* 
 }
 
 // X (in x0) -> NS(X): after `steps` iterations the result is in x0 for an even count, in x1 for an odd one.
-int muon_newton_schulz(void* x0, void* x1, void* amat, void* bmat, float* da, float* db, const int32_t* tab, int nprob, int tiles_sym,
-                       int tiles_full, int steps, double a, double b, double c, int normalize, float* partials,
-                       hipStream_t st) {
+extern "C" int saicv_muon_newton_schulz(void* x0, void* x1, void* amat, void* bmat, float* da, float* db, const int32_t* tab, int nprob, int tiles_sym,
+                                        int tiles_full, int steps, double a, double b, double c, int normalize, float* partials,
+                                        void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(nprob >= 0 && steps >= 0, "muon_newton_schulz: %d problems, %d steps", nprob, steps);
     if (nprob == 0) return 0;
     SAICV_REQUIRE(x0 && x1 && amat && bmat && da && db && tab && tiles_sym > 0 && tiles_full > 0,
@@ -356,8 +359,9 @@ int muon_newton_schulz(void* x0, void* x1, void* amat, void* bmat, float* da, fl
     return check_launch("muon_newton_schulz");
 }
 
-int muon_apply(float* p, const void* uws, const int32_t* block_prob, const int32_t* tab, const float* hyper,
-               const float* found_inf, const uint8_t* has_grad, size_t n, hipStream_t st) {
+extern "C" int saicv_muon_apply(float* p, const void* uws, const int32_t* block_prob, const int32_t* tab, const float* hyper,
+                                const float* found_inf, const uint8_t* has_grad, size_t n, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(n % 1024 == 0 && n > 0, "muon_apply: arena length %zu must be a positive multiple of 1024", n);
     hipLaunchKernelGGL(muon_apply_kernel, dim3((unsigned)(n / 1024)), dim3(256), 0, st, p, (const bf16_t*)uws, block_prob, tab, hyper,
                        found_inf, has_grad);

@@ -7,6 +7,7 @@
 // tools/utils.py:292-679 (build_optimizer) and GradScaler (tools/utils.py:199-200).
 #include "common.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 #include "det.h"
 
 // cache policy of the fused optimizer kernels: the default one (streaming loads and stores -- every value is read once and written
@@ -184,23 +185,26 @@ __global__ void scaler_update_kernel(float* __restrict__ state, const float* __r
 
 namespace saicv {
 
-int sgd_flat(float* p, const float* g, float* mom, const int32_t* block_group, const float* hyper,
-             const float* inv_scale, const float* found_inf, const uint8_t* has_grad, size_t n, hipStream_t st) {
+extern "C" int saicv_sgd_flat(float* p, const float* g, float* mom, const int32_t* block_group, const float* hyper,
+                              const float* inv_scale, const float* found_inf, const uint8_t* has_grad, size_t n, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(n % 1024 == 0, "sgd_flat: arena length %zu must be a multiple of 1024", n);
     hipLaunchKernelGGL(sgd_flat_kernel, dim3((unsigned)(n / 1024)), dim3(256), 0, st, p, g, mom, block_group, hyper, inv_scale, found_inf, has_grad, n);
     return check_launch("sgd_flat");
 }
 
-int adamw_flat(float* p, const float* g, float* m, float* v, const int32_t* block_group,
-               const float* hyper, const float* inv_scale, const float* found_inf, const uint8_t* has_grad,
-               float* step_blk, size_t n, hipStream_t st) {
+extern "C" int saicv_adamw_flat(float* p, const float* g, float* m, float* v, const int32_t* block_group,
+                                const float* hyper, const float* inv_scale, const float* found_inf, const uint8_t* has_grad,
+                                float* step_blk, size_t n, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(step_blk != nullptr, "adamw_flat: the per-block step counters are required");
     SAICV_REQUIRE(n % 1024 == 0, "adamw_flat: arena length %zu must be a multiple of 1024", n);
     hipLaunchKernelGGL(adamw_flat_kernel, dim3((unsigned)(n / 1024)), dim3(256), 0, st, p, g, m, v, block_group, hyper, inv_scale, found_inf, has_grad, step_blk, n);
     return check_launch("adamw_flat");
 }
 
-int grad_stats(const float* g, size_t n, float* found_inf, float* sumsq, hipStream_t st) {
+extern "C" int saicv_grad_stats(const float* g, size_t n, float* found_inf, float* sumsq, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(n % 4 == 0, "grad_stats: length %zu must be a multiple of 4", n);
     size_t b = (n / 4 + 255) / 256;
     if (b > 2048) b = 2048;
@@ -212,8 +216,9 @@ int grad_stats(const float* g, size_t n, float* found_inf, float* sumsq, hipStre
     return det.fold(sumsq, 0, 1);
 }
 
-int grad_clip_scale(float* g, size_t n, const float* sumsq, const float* inv_scale, double max_norm,
-                    hipStream_t st) {
+extern "C" int saicv_grad_clip_scale(float* g, size_t n, const float* sumsq, const float* inv_scale, double max_norm,
+                                     void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(n % 4 == 0, "grad_clip_scale: length %zu must be a multiple of 4", n);
     size_t b = (n / 4 + 255) / 256;
     if (b > 2048) b = 2048;
@@ -222,7 +227,8 @@ int grad_clip_scale(float* g, size_t n, const float* sumsq, const float* inv_sca
     return check_launch("grad_clip_scale");
 }
 
-int grad_clip_value(float* g, size_t n, const float* inv_scale, double value, hipStream_t st) {
+extern "C" int saicv_grad_clip_value(float* g, size_t n, const float* inv_scale, double value, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(n % 4 == 0 && value > 0, "grad_clip_value: length %zu must be a multiple of 4, the bound positive", n);
     size_t b = (n / 4 + 255) / 256;
     if (b > 2048) b = 2048;
@@ -231,8 +237,9 @@ int grad_clip_value(float* g, size_t n, const float* inv_scale, double value, hi
     return check_launch("grad_clip_value");
 }
 
-int scaler_update(float* state, const float* found_inf, double growth, double backoff, int interval,
-                  hipStream_t st) {
+extern "C" int saicv_scaler_update(float* state, const float* found_inf, double growth, double backoff, int interval,
+                                   void* stream) {
+    hipStream_t st = S(stream);
     hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(64), 0, st, state, found_inf, (float)growth, (float)backoff, interval);
     return check_launch("scaler_update");
 }

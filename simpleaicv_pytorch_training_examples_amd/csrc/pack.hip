@@ -305,8 +305,9 @@ inline int sgrid(size_t total) {
 
 namespace saicv {
 
-int pack_input(int dtype, const float* src, long sN, long sC, long sH, long sW, void* dst, int Nimg,
-               int C, int H, int W, int Cp, hipStream_t st) {
+extern "C" int saicv_pack_input(int dtype, const float* src, long sN, long sC, long sH, long sW, void* dst, int Nimg,
+                                int C, int H, int W, int Cp, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(Cp >= C, "pack_input: Cp=%d < C=%d", Cp, C);
     const size_t total = (size_t)Nimg * H * W;
     if (dtype == SAICV_DTYPE_BF16)
@@ -316,8 +317,9 @@ int pack_input(int dtype, const float* src, long sN, long sC, long sH, long sW, 
     return check_launch("pack_input");
 }
 
-int pack_weight(int dtype, const float* w, long sO, long sI, long sR, long sS, int O, int I, int R,
-                int S, int Ip, int Op, void* wf, void* wd, hipStream_t st) {
+extern "C" int saicv_pack_weight(int dtype, const float* w, long sO, long sI, long sR, long sS, int O, int I, int R,
+                                 int S, int Ip, int Op, void* wf, void* wd, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     SAICV_REQUIRE(Ip >= I, "pack_weight: Ip=%d < I=%d", Ip, I);
     SAICV_REQUIRE(wd == nullptr || Ip == I, "pack_weight: data-gradient matrix needs unpadded I");
     SAICV_REQUIRE(Op >= O, "pack_weight: Op=%d < O=%d", Op, O);
@@ -330,7 +332,8 @@ int pack_weight(int dtype, const float* w, long sO, long sI, long sR, long sS, i
     return check_launch("pack_weight");
 }
 
-int pack_weight_batched(int dtype, const saicv_pack_desc* descs, int n, int total_tiles, hipStream_t st) {
+extern "C" int saicv_pack_weight_batched(int dtype, const saicv_pack_desc* descs, int n, int total_tiles, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(descs != nullptr && n > 0 && total_tiles > 0, "pack_weight_batched: empty descriptor table");
     if (dtype == SAICV_DTYPE_BF16)
         hipLaunchKernelGGL(pack_weight_batched_kernel<bf16_t>, dim3(total_tiles), dim3(256), 0, st, descs, n);
@@ -339,15 +342,17 @@ int pack_weight_batched(int dtype, const saicv_pack_desc* descs, int n, int tota
     return check_launch("pack_weight_batched");
 }
 
-int unpack_wgrad(const float* dw, int O, int I, int R, int S, int Ip, float* g, long sO, long sI,
-                 long sR, long sS, int accumulate, hipStream_t st) {
+extern "C" int saicv_unpack_wgrad(const float* dw, int O, int I, int R, int S, int Ip, float* g, long sO, long sI,
+                                  long sR, long sS, int accumulate, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t total = (size_t)O * R * S * I;
     hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(sgrid(total)), dim3(256), 0, st, dw, O, I, R, S, Ip, g, sO, sI, sR, sS, accumulate);
     return check_launch("unpack_wgrad");
 }
 
-int pack_input_s2d(int dtype, const float* src, long sN, long sC, long sH, long sW, void* dst, int Nimg, int C, int H,
-                   int W, int pad, int Cq, hipStream_t st) {
+extern "C" int saicv_pack_input_s2d(int dtype, const float* src, long sN, long sC, long sH, long sW, void* dst, int Nimg, int C, int H,
+                                    int W, int pad, int Cq, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(Cq >= 4 * C && pad >= 0, "pack_input_s2d: Cq=%d < 4*C=%d", Cq, 4 * C);
     const int Hq = (H + 2 * pad + 1) / 2, Wq = (W + 2 * pad + 1) / 2;
     const size_t total = (size_t)Nimg * Hq * Wq * 4;
@@ -358,8 +363,9 @@ int pack_input_s2d(int dtype, const float* src, long sN, long sC, long sH, long 
     return check_launch("pack_input_s2d");
 }
 
-int pack_weight_s2d(int dtype, const float* w, long sO, long sI, long sR, long sS, int O, int I, int R, int S, int Cq,
-                    void* wf, hipStream_t st) {
+extern "C" int saicv_pack_weight_s2d(int dtype, const float* w, long sO, long sI, long sR, long sS, int O, int I, int R, int S, int Cq,
+                                     void* wf, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     SAICV_REQUIRE(Cq >= 4 * I, "pack_weight_s2d: Cq=%d < 4*I=%d", Cq, 4 * I);
     const int R2 = (R + 1) / 2, S2 = (S + 1) / 2;
     const size_t total = (size_t)O * R2 * S2 * Cq;
@@ -370,16 +376,18 @@ int pack_weight_s2d(int dtype, const float* w, long sO, long sI, long sR, long s
     return check_launch("pack_weight_s2d");
 }
 
-int unpack_wgrad_s2d(const float* dw, int O, int I, int R, int S, int Cq, float* g, long sO, long sI, long sR, long sS,
-                     int accumulate, hipStream_t st) {
+extern "C" int saicv_unpack_wgrad_s2d(const float* dw, int O, int I, int R, int S, int Cq, float* g, long sO, long sI, long sR, long sS,
+                                      int accumulate, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t total = (size_t)O * R * S * I;
     hipLaunchKernelGGL(unpack_wgrad_s2d_kernel, dim3(sgrid(total)), dim3(256), 0, st, dw, O, I, R, S, (R + 1) / 2, (S + 1) / 2, Cq, g,
                        sO, sI, sR, sS, accumulate);
     return check_launch("unpack_wgrad_s2d");
 }
 
-int row_scale(int dtype, const void* x, const float* scale, void* out, size_t rows, int row_len,
-              int rows_per_scale, hipStream_t st) {
+extern "C" int saicv_row_scale(int dtype, const void* x, const float* scale, void* out, size_t rows, int row_len,
+                               int rows_per_scale, void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(row_len % n == 0 && rows_per_scale >= 1, "row_scale: row length %d must be a multiple of %d", row_len, n);
     const size_t nchunks = rows * (size_t)(row_len / n);
@@ -391,7 +399,8 @@ int row_scale(int dtype, const void* x, const float* scale, void* out, size_t ro
     return check_launch("row_scale");
 }
 
-int colsum(int dtype, const void* x, int M, int N, float* out, hipStream_t st) {
+extern "C" int saicv_colsum(int dtype, const void* x, int M, int N, float* out, void* stream) {
+    hipStream_t st = S(stream);
     const int e = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(N % e == 0, "colsum: N=%d must be a multiple of %d", N, e);
     const int cpr = N / e;

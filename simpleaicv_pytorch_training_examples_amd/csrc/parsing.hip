@@ -29,6 +29,7 @@
 #include "ordered_sum.h"
 #include "rowspan.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 
 namespace {
 
@@ -388,12 +389,13 @@ void pct_launch_bwd(const T* logits, const float* label, const float* g, int row
 namespace saicv {
 
 // enough for either form: three partials per workgroup of the smaller tile
-size_t pixel_class_terms_ws_floats(size_t rows) { return 3 * ((rows + PCT_WAVE_ROWS - 1) / PCT_WAVE_ROWS); }
+extern "C" size_t saicv_pixel_class_terms_ws_floats(size_t rows) { return 3 * ((rows + PCT_WAVE_ROWS - 1) / PCT_WAVE_ROWS); }
 
-int pixel_class_terms_lane_max_classes() { return PCT_LANE_MAX_C; }
+extern "C" int saicv_pixel_class_terms_lane_max_classes() { return PCT_LANE_MAX_C; }
 
-int pixel_class_terms_fwd(int dtype, const void* logits, const float* label, size_t rows, int C, int sigmoid, int form,
-                          float* partial, float* terms, hipStream_t st) {
+extern "C" int saicv_pixel_class_terms_fwd(int dtype, const void* logits, const float* label, size_t rows, int C, int sigmoid, int form,
+                                           float* partial, float* terms, void* stream) {
+    hipStream_t st = S(stream);
     if (pct_check("pixel_class_terms_fwd", logits, label, rows, C, form)) return -1;
     SAICV_REQUIRE(partial != nullptr && terms != nullptr, "pixel_class_terms_fwd: null workspace or output");
     const bool lane = pct_lane_form(C, form);
@@ -409,8 +411,9 @@ int pixel_class_terms_fwd(int dtype, const void* logits, const float* label, siz
     return check_launch("pixel_class_terms_fwd");
 }
 
-int pixel_class_terms_bwd(int dtype, const void* logits, const float* label, const float* gterms, size_t rows, int C, int sigmoid,
-                          int form, void* dlogits, hipStream_t st) {
+extern "C" int saicv_pixel_class_terms_bwd(int dtype, const void* logits, const float* label, const float* gterms, size_t rows, int C, int sigmoid,
+                                           int form, void* dlogits, void* stream) {
+    hipStream_t st = S(stream);
     if (pct_check("pixel_class_terms_bwd", logits, label, rows, C, form)) return -1;
     SAICV_REQUIRE(gterms != nullptr, "pixel_class_terms_bwd: null dL/dterms");
     SAICV_REQUIRE(dlogits != nullptr && ((uintptr_t)dlogits & 15) == 0,

@@ -4,6 +4,7 @@
 // HBM-bound streaming kernels; one 16-byte chunk of channels per thread.
 #include "common.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 #include "det.h"
 #include "poolbwd.h"
 
@@ -554,8 +555,9 @@ inline int sgrid(size_t total) {
 
 namespace saicv {
 
-int maxpool_fwd(int dtype, const void* x, void* out, uint8_t* idx, int Nimg, int H, int W, int C,
-                int OH, int OW, int K, int stride, int pad, hipStream_t st) {
+extern "C" int saicv_maxpool_fwd(int dtype, const void* x, void* out, uint8_t* idx, int Nimg, int H, int W, int C,
+                                 int OH, int OW, int K, int stride, int pad, void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0, "maxpool_fwd: C=%d must be a multiple of %d", C, n);
     SAICV_REQUIRE(K * K <= 255, "maxpool_fwd: window too large");
@@ -567,8 +569,9 @@ int maxpool_fwd(int dtype, const void* x, void* out, uint8_t* idx, int Nimg, int
     return check_launch("maxpool_fwd");
 }
 
-int maxpool_bwd(int dtype, const void* dout, const uint8_t* idx, void* dx, int Nimg, int H, int W,
-                int C, int OH, int OW, int K, int stride, int pad, hipStream_t st) {
+extern "C" int saicv_maxpool_bwd(int dtype, const void* dout, const uint8_t* idx, void* dx, int Nimg, int H, int W,
+                                 int C, int OH, int OW, int K, int stride, int pad, void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0, "maxpool_bwd: C=%d must be a multiple of %d", C, n);
     SAICV_REQUIRE(K * K <= 255, "maxpool_bwd: window too large");
@@ -599,13 +602,15 @@ static int bn_relu_maxpool_fwd_launch(int dtype, const void* y, const float* sca
     return check_launch("bn_relu_maxpool_fwd");
 }
 
-int bn_relu_maxpool_fwd(int dtype, const void* y, const float* scale, const float* shift, void* out, uint8_t* idx, int Nimg, int H,
-                        int W, int C, int OH, int OW, int K, int stride, int pad, hipStream_t st) {
+extern "C" int saicv_bn_relu_maxpool_fwd(int dtype, const void* y, const float* scale, const float* shift, void* out, uint8_t* idx, int Nimg, int H,
+                                         int W, int C, int OH, int OW, int K, int stride, int pad, void* stream) {
+    hipStream_t st = S(stream);
     return bn_relu_maxpool_fwd_launch(dtype, y, scale, shift, out, idx, nullptr, Nimg, H, W, C, OH, OW, K, stride, pad, st);
 }
 
-int bn_relu_maxpool_fwd_keep(int dtype, const void* y, const float* scale, const float* shift, void* out, uint8_t* idx, void* ya,
-                             int Nimg, int H, int W, int C, int OH, int OW, int K, int stride, int pad, hipStream_t st) {
+extern "C" int saicv_bn_relu_maxpool_fwd_keep(int dtype, const void* y, const float* scale, const float* shift, void* out, uint8_t* idx, void* ya,
+                                              int Nimg, int H, int W, int C, int OH, int OW, int K, int stride, int pad, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(ya != nullptr, "bn_relu_maxpool_fwd_keep: ya missing");
     return bn_relu_maxpool_fwd_launch(dtype, y, scale, shift, out, idx, ya, Nimg, H, W, C, OH, OW, K, stride, pad, st);
 }
@@ -613,8 +618,9 @@ int bn_relu_maxpool_fwd_keep(int dtype, const void* y, const float* scale, const
 // The two per-channel sums of bn_relu_maxpool_bwd's first pass from the maxima the forward kept: sums[0][c] = sum g, sums[1][c] =
 // sum g * xhat over the pooled elements, g = dout * [scale * ya + shift > 0].  Grid, thread -> element mapping, accumulation order,
 // LDS reduction and partial index are those of the pass over y, so the sums are its sums (bit for bit in deterministic mode).
-int bn_relu_maxpool_bwd_sums(int dtype, const void* dout, const void* ya, const float* mean, const float* invstd, const float* scale,
-                             const float* shift, float* sums, int Nimg, int OH, int OW, int C, hipStream_t st) {
+extern "C" int saicv_bn_relu_maxpool_bwd_sums(int dtype, const void* dout, const void* ya, const float* mean, const float* invstd, const float* scale,
+                                              const float* shift, float* sums, int Nimg, int OH, int OW, int C, void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0 && 256 % (C / n) == 0, "bn_relu_maxpool_bwd_sums: C=%d must be %d x a power of two <= 256", C, n);
     SAICV_REQUIRE(Nimg > 0 && OH > 0 && OW > 0, "bn_relu_maxpool_bwd_sums: empty tensor");
@@ -631,10 +637,11 @@ int bn_relu_maxpool_bwd_sums(int dtype, const void* dout, const void* ya, const 
 }
 
 // The second pass alone, from given sums ([2][C]: of the first pass below, or of bn_relu_maxpool_bwd_sums): dy, dgamma, dbeta
-int bn_relu_maxpool_bwd_apply(int dtype, const void* dout, const uint8_t* idx, const void* y, const float* gamma, const float* mean,
-                              const float* invstd, const float* scale, const float* shift, const float* sums, void* dy, float* dgamma,
-                              float* dbeta, int accumulate, int Nimg, int H, int W, int C, int OH, int OW, int K, int stride, int pad,
-                              hipStream_t st) {
+extern "C" int saicv_bn_relu_maxpool_bwd_apply(int dtype, const void* dout, const uint8_t* idx, const void* y, const float* gamma, const float* mean,
+                                               const float* invstd, const float* scale, const float* shift, const float* sums, void* dy, float* dgamma,
+                                               float* dbeta, int accumulate, int Nimg, int H, int W, int C, int OH, int OW, int K, int stride, int pad,
+                                               void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0 && 256 % (C / n) == 0, "bn_relu_maxpool_bwd: C=%d must be %d x a power of two <= 256", C, n);
     SAICV_REQUIRE(K <= 2 * stride + 1, "bn_relu_maxpool_bwd: K=%d, stride=%d: more than 2 x 2 windows cover a pixel", K, stride);
@@ -652,10 +659,11 @@ int bn_relu_maxpool_bwd_apply(int dtype, const void* dout, const uint8_t* idx, c
     return check_launch("bn_relu_maxpool_bwd");
 }
 
-int bn_relu_maxpool_bwd(int dtype, const void* dout, const uint8_t* idx, const void* y, const float* gamma, const float* mean,
-                        const float* invstd, const float* scale, const float* shift, void* dy, float* dgamma, float* dbeta,
-                        int accumulate, float* ws, int Nimg, int H, int W, int C, int OH, int OW, int K, int stride, int pad,
-                        hipStream_t st) {
+extern "C" int saicv_bn_relu_maxpool_bwd(int dtype, const void* dout, const uint8_t* idx, const void* y, const float* gamma, const float* mean,
+                                         const float* invstd, const float* scale, const float* shift, void* dy, float* dgamma, float* dbeta,
+                                         int accumulate, float* ws, int Nimg, int H, int W, int C, int OH, int OW, int K, int stride, int pad,
+                                         void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0 && 256 % (C / n) == 0, "bn_relu_maxpool_bwd: C=%d must be %d x a power of two <= 256", C, n);
     SAICV_REQUIRE(K <= 2 * stride + 1, "bn_relu_maxpool_bwd: K=%d, stride=%d: more than 2 x 2 windows cover a pixel", K, stride);
@@ -671,11 +679,12 @@ int bn_relu_maxpool_bwd(int dtype, const void* dout, const uint8_t* idx, const v
         else hipLaunchKernelGGL((bn_relu_maxpool_bwd_reduce_kernel<float, 0>), dim3(sgrid(ptotal)), dim3(256), 0, st, (const float*)dout, idx, (const float*)y, mean, invstd, scale, shift, ws, Nimg, H, W, C, OH, OW, K, stride, pad, det.sink());
     }
     if (det.fold(ws, 0, (size_t)2 * C)) return -1;
-    return bn_relu_maxpool_bwd_apply(dtype, dout, idx, y, gamma, mean, invstd, scale, shift, ws, dy, dgamma, dbeta, accumulate, Nimg, H, W, C,
-                                     OH, OW, K, stride, pad, st);
+    return saicv_bn_relu_maxpool_bwd_apply(dtype, dout, idx, y, gamma, mean, invstd, scale, shift, ws, dy, dgamma, dbeta, accumulate, Nimg, H, W, C,
+                                           OH, OW, K, stride, pad, st);
 }
 
-int avgpool_fwd(int dtype, const void* x, void* out, int Nimg, int HW, int C, hipStream_t st) {
+extern "C" int saicv_avgpool_fwd(int dtype, const void* x, void* out, int Nimg, int HW, int C, void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0, "avgpool_fwd: C=%d must be a multiple of %d", C, n);
     const size_t total = (size_t)Nimg * (C / n);
@@ -687,7 +696,8 @@ int avgpool_fwd(int dtype, const void* x, void* out, int Nimg, int HW, int C, hi
     return check_launch("avgpool_fwd");
 }
 
-int avgpool_bwd(int dtype, const void* dout, void* dx, int Nimg, int HW, int C, hipStream_t st) {
+extern "C" int saicv_avgpool_bwd(int dtype, const void* dout, void* dx, int Nimg, int HW, int C, void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0, "avgpool_bwd: C=%d must be a multiple of %d", C, n);
     const size_t total = (size_t)Nimg * HW * (C / n);

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "ordered_sum.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 
 namespace {
 
@@ -366,13 +367,14 @@ int bss_vec(const void* a, const void* b, const void* c, size_t P) {
 
 namespace saicv {
 
-size_t conv3x3_c1_ws_floats(int N, int H, int W, int C) {
+extern "C" size_t saicv_conv3x3_c1_ws_floats(int N, int H, int W, int C) {
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
     return (size_t)N * ((H + C1_BH - 1) / C1_BH) * ((W + C1_BW - 1) / C1_BW) * (size_t)(9 * C + 1);
 }
 
-int conv3x3_c1_fwd(int dtype, const void* x, const float* weight, long wsc, long wsk, const float* bias, float* out, int N, int H,
-                   int W, int C, int sigmoid, hipStream_t st) {
+extern "C" int saicv_conv3x3_c1_fwd(int dtype, const void* x, const float* weight, long wsc, long wsk, const float* bias, float* out, int N, int H,
+                                    int W, int C, int sigmoid, void* stream) {
+    hipStream_t st = S(stream);
     C1Geom g;
     if (c1_geom(g, "conv3x3_c1_fwd", dtype, x, N, H, W, C, wsc, wsk, sigmoid, C1_TH, C1_TW)) return -1;
     SAICV_REQUIRE(weight != nullptr && bias != nullptr && out != nullptr, "conv3x3_c1_fwd: null weight, bias or output");
@@ -394,8 +396,9 @@ int conv3x3_c1_fwd(int dtype, const void* x, const float* weight, long wsc, long
     return check_launch("conv3x3_c1_fwd");
 }
 
-int conv3x3_c1_bwd(int dtype, const void* x, const float* weight, long wsc, long wsk, const float* p, const float* dout, void* dx,
-                   float* dw, float* db, float* ws, int N, int H, int W, int C, int sigmoid, int accumulate, hipStream_t st) {
+extern "C" int saicv_conv3x3_c1_bwd(int dtype, const void* x, const float* weight, long wsc, long wsk, const float* p, const float* dout, void* dx,
+                                    float* dw, float* db, float* ws, int N, int H, int W, int C, int sigmoid, int accumulate, void* stream) {
+    hipStream_t st = S(stream);
     C1Geom g;
     if (c1_geom(g, "conv3x3_c1_bwd", dtype, x, N, H, W, C, wsc, wsk, sigmoid, C1_BH, C1_BW)) return -1;
     SAICV_REQUIRE(weight != nullptr && dout != nullptr && ws != nullptr, "conv3x3_c1_bwd: null weight, gradient or workspace");
@@ -414,12 +417,13 @@ int conv3x3_c1_bwd(int dtype, const void* x, const float* weight, long wsc, long
     return check_launch("conv3x3_c1_bwd");
 }
 
-size_t binary_seg_stats_ws_floats(int B, size_t P) {
+extern "C" size_t saicv_binary_seg_stats_ws_floats(int B, size_t P) {
     if (B <= 0 || P == 0) return 0;
     return (size_t)B * ((P + BSS_SPAN - 1) / BSS_SPAN) * 4;
 }
 
-int binary_seg_stats_fwd(const float* prob, const float* label, int B, size_t P, float* partial, float* stats, hipStream_t st) {
+extern "C" int saicv_binary_seg_stats_fwd(const float* prob, const float* label, int B, size_t P, float* partial, float* stats, void* stream) {
+    hipStream_t st = S(stream);
     if (bss_check("binary_seg_stats_fwd", prob, label, B, P)) return -1;
     SAICV_REQUIRE(partial != nullptr && stats != nullptr, "binary_seg_stats_fwd: null workspace or output");
     const int nblk = (int)((P + BSS_SPAN - 1) / BSS_SPAN);
@@ -428,7 +432,8 @@ int binary_seg_stats_fwd(const float* prob, const float* label, int B, size_t P,
     return check_launch("binary_seg_stats_fwd");
 }
 
-int binary_seg_stats_bwd(const float* prob, const float* label, const float* gstats, int B, size_t P, float* dprob, hipStream_t st) {
+extern "C" int saicv_binary_seg_stats_bwd(const float* prob, const float* label, const float* gstats, int B, size_t P, float* dprob, void* stream) {
+    hipStream_t st = S(stream);
     if (bss_check("binary_seg_stats_bwd", prob, label, B, P)) return -1;
     SAICV_REQUIRE(gstats != nullptr && dprob != nullptr, "binary_seg_stats_bwd: null gradient");
     const int nblk = (int)((P + BSS_SPAN - 1) / BSS_SPAN);

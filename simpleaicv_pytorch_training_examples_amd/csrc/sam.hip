@@ -11,6 +11,7 @@
 // All are HBM / latency bound; activations are bf16 (perf mode) or fp32 (parity mode).
 #include "common.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 #include "det.h"
 
 namespace {
@@ -608,7 +609,8 @@ static int window_check(const char* who, int dtype, int B, int H, int W, int C, 
     return 0;
 }
 
-int window_partition(int dtype, const void* x, void* out, int B, int H, int W, int C, int ws, hipStream_t st) {
+extern "C" int saicv_window_partition(int dtype, const void* x, void* out, int B, int H, int W, int C, int ws, void* stream) {
+    hipStream_t st = S(stream);
     if (window_check("window_partition", dtype, B, H, W, C, ws)) return -1;
     const int nwh = (H + ws - 1) / ws, nww = (W + ws - 1) / ws;
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
@@ -620,8 +622,9 @@ int window_partition(int dtype, const void* x, void* out, int B, int H, int W, i
     return check_launch("window_partition");
 }
 
-int window_unpartition(int dtype, const void* win, const void* addend, void* out, int B, int H, int W, int C, int ws,
-                       hipStream_t st) {
+extern "C" int saicv_window_unpartition(int dtype, const void* win, const void* addend, void* out, int B, int H, int W, int C, int ws,
+                                        void* stream) {
+    hipStream_t st = S(stream);
     if (window_check("window_unpartition", dtype, B, H, W, C, ws)) return -1;
     const int nwh = (H + ws - 1) / ws, nww = (W + ws - 1) / ws;
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
@@ -642,8 +645,9 @@ static int relpos_fill(RelPosParams& p, const char* who, int dtype, const void* 
     return 0;
 }
 
-int relpos_fwd(int dtype, const void* q, long q_rs, long q_bs, const float* tab_h, const float* tab_w, float* rel_h,
-               float* rel_w, int B, int heads, int Sh, int Sw, hipStream_t st) {
+extern "C" int saicv_relpos_fwd(int dtype, const void* q, long q_rs, long q_bs, const float* tab_h, const float* tab_w, float* rel_h,
+                                float* rel_w, int B, int heads, int Sh, int Sw, void* stream) {
+    hipStream_t st = S(stream);
     RelPosParams p = {};
     if (relpos_fill(p, "relpos_fwd", dtype, q, q_rs, q_bs, tab_h, tab_w, B, heads, Sh, Sw)) return -1;
     p.rel_h = rel_h; p.rel_w = rel_w;
@@ -659,11 +663,12 @@ int relpos_fwd(int dtype, const void* q, long q_rs, long q_bs, const float* tab_
     return check_launch("relpos_fwd");
 }
 
-size_t relpos_bwd_ws_floats(int Sh, int Sw) { return (size_t)RP_COPIES * (2 * Sh - 1 + 2 * Sw - 1) * RP_D; }
+extern "C" size_t saicv_relpos_bwd_ws_floats(int Sh, int Sw) { return (size_t)RP_COPIES * (2 * Sh - 1 + 2 * Sw - 1) * RP_D; }
 
-int relpos_bwd(int dtype, const void* q, void* dq, long q_rs, long q_bs, const float* tab_h, const float* tab_w,
-               const float* d_rel_h, const float* d_rel_w, float* dtab_h, float* dtab_w, float* ws, int B, int heads, int Sh,
-               int Sw, hipStream_t st) {
+extern "C" int saicv_relpos_bwd(int dtype, const void* q, void* dq, long q_rs, long q_bs, const float* tab_h, const float* tab_w,
+                                const float* d_rel_h, const float* d_rel_w, float* dtab_h, float* dtab_w, float* ws, int B, int heads, int Sh,
+                                int Sw, void* stream) {
+    hipStream_t st = S(stream);
     RelPosParams p = {};
     if (relpos_fill(p, "relpos_bwd", dtype, q, q_rs, q_bs, tab_h, tab_w, B, heads, Sh, Sw)) return -1;
     SAICV_REQUIRE((dtab_h == nullptr) == (dtab_w == nullptr) && (dtab_h == nullptr || ws != nullptr),
@@ -680,7 +685,7 @@ int relpos_bwd(int dtype, const void* q, void* dq, long q_rs, long q_bs, const f
         p.dtab_h = det.sink().part; p.dtab_w = det.sink().part + n_h;
         p.copies = Sh * B;
     } else if (dtab_h) {
-        hipMemsetAsync(ws, 0, relpos_bwd_ws_floats(Sh, Sw) * sizeof(float), st);
+        hipMemsetAsync(ws, 0, saicv_relpos_bwd_ws_floats(Sh, Sw) * sizeof(float), st);
     }
     const size_t smem1 = (size_t)(Sh + 2 * Sw - 1) * RP_PITCH * sizeof(float);
     const int nh = (Sh + 15) / 16, nw = (2 * Sw - 1 + 15) / 16;

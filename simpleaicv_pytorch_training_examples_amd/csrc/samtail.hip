@@ -18,6 +18,7 @@
 // i0 = floor(src), i1 = min(i0 + 1, n - 1), l1 = src - i0, l0 = 1 - l1; out = l0h (l0w v00 + l1w v01) + l1h (l0w v10 + l1w v11).
 #include "common.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 #include "det.h"
 #include "maskterm.h"
 #include "ordered_sum.h"
@@ -276,7 +277,8 @@ __global__ __launch_bounds__(GU_T * GU_T) void grad_up4_tiled_kernel(const T* __
 
 namespace saicv {
 
-int hyper_product_fwd(int dtype, const void* x, const void* hyper, void* out, int B, int Tm, int P, int C, hipStream_t st) {
+extern "C" int saicv_hyper_product_fwd(int dtype, const void* x, const void* hyper, void* out, int B, int Tm, int P, int C, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(C == 32, "hyper_product: C=%d (the mask decoder's upscaled embedding has 32 channels)", C);
     SAICV_REQUIRE(B > 0 && P > 0 && Tm >= 1 && Tm <= 8, "hyper_product: bad sizes B=%d P=%d T=%d", B, P, Tm);
     dim3 grid((P + ST_THREADS - 1) / ST_THREADS, B);
@@ -287,8 +289,9 @@ int hyper_product_fwd(int dtype, const void* x, const void* hyper, void* out, in
     return check_launch("hyper_product_fwd");
 }
 
-int hyper_product_bwd(int dtype, const void* x, const void* hyper, const void* dout, void* dx, float* dhyper, int B, int Tm,
-                      int P, int C, hipStream_t st) {
+extern "C" int saicv_hyper_product_bwd(int dtype, const void* x, const void* hyper, const void* dout, void* dx, float* dhyper, int B, int Tm,
+                                       int P, int C, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(C == 32, "hyper_product: C=%d (the mask decoder's upscaled embedding has 32 channels)", C);
     SAICV_REQUIRE(B > 0 && P > 0 && Tm >= 1 && Tm <= 8, "hyper_product: bad sizes B=%d P=%d T=%d", B, P, Tm);
     hipMemsetAsync(dhyper, 0, (size_t)B * Tm * C * sizeof(float), st);
@@ -306,7 +309,8 @@ int hyper_product_bwd(int dtype, const void* x, const void* hyper, const void* d
 #define UP4_CHECK(who)                                                                                                   \
     SAICV_REQUIRE(planes > 0 && h > 0 && w > 0 && h <= 65535 && planes <= 65535, who ": bad sizes planes=%d h=%d w=%d", planes, h, w)
 
-int upsample4_fwd(int dtype, const void* low, void* out, int planes, int h, int w, hipStream_t st) {
+extern "C" int saicv_upsample4_fwd(int dtype, const void* low, void* out, int planes, int h, int w, void* stream) {
+    hipStream_t st = S(stream);
     UP4_CHECK("upsample4_fwd");
     dim3 grid((w + ST_THREADS - 1) / ST_THREADS, h, planes);
     if (dtype == SAICV_DTYPE_BF16) hipLaunchKernelGGL(up4_fwd_kernel<bf16_t>, grid, dim3(ST_THREADS), 0, st, (const bf16_t*)low, (bf16_t*)out, h, w);
@@ -314,7 +318,8 @@ int upsample4_fwd(int dtype, const void* low, void* out, int planes, int h, int 
     return check_launch("upsample4_fwd");
 }
 
-int upsample4_bwd(int dtype, const void* dhi, void* dlow, int planes, int h, int w, hipStream_t st) {
+extern "C" int saicv_upsample4_bwd(int dtype, const void* dhi, void* dlow, int planes, int h, int w, void* stream) {
+    hipStream_t st = S(stream);
     UP4_CHECK("upsample4_bwd");
     dim3 grid((w + ST_THREADS - 1) / ST_THREADS, h, planes);
     if (dtype == SAICV_DTYPE_BF16) hipLaunchKernelGGL(up4_bwd_kernel<bf16_t>, grid, dim3(ST_THREADS), 0, st, (const bf16_t*)dhi, (bf16_t*)dlow, h, w);
@@ -322,8 +327,9 @@ int upsample4_bwd(int dtype, const void* dhi, void* dlow, int planes, int h, int
     return check_launch("upsample4_bwd");
 }
 
-int mask_loss_stats_up4(int dtype, const void* low, const float* targets, float* stats, int B, int M, int h, int w,
-                        double alpha, double gamma, double thr, hipStream_t st) {
+extern "C" int saicv_mask_loss_stats_up4(int dtype, const void* low, const float* targets, float* stats, int B, int M, int h, int w,
+                                         double alpha, double gamma, double thr, void* stream) {
+    hipStream_t st = S(stream);
     const int planes = B * M;
     UP4_CHECK("mask_loss_stats_up4");
     hipMemsetAsync(stats, 0, (size_t)planes * 6 * sizeof(float), st);
@@ -338,8 +344,9 @@ int mask_loss_stats_up4(int dtype, const void* low, const float* targets, float*
     return det.fold(stats, 0, (size_t)planes * 6);
 }
 
-int mask_loss_grad_up4(int dtype, const void* low, const float* targets, const float* coef, void* dlow, int B, int M, int h,
-                       int w, double alpha, double gamma, hipStream_t st) {
+extern "C" int saicv_mask_loss_grad_up4(int dtype, const void* low, const float* targets, const float* coef, void* dlow, int B, int M, int h,
+                                        int w, double alpha, double gamma, void* stream) {
+    hipStream_t st = S(stream);
     const int planes = B * M;
     UP4_CHECK("mask_loss_grad_up4");
     dim3 tgrid((w + GU_T - 1) / GU_T, (h + GU_T - 1) / GU_T, planes);

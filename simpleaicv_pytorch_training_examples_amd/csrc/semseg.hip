@@ -22,6 +22,7 @@
 #include "ordered_sum.h"
 #include "rowspan.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 
 namespace {
 
@@ -235,7 +236,7 @@ int grid_for(size_t total) {
 
 namespace saicv {
 
-size_t pixel_softmax_ce_ws_floats(size_t rows) { return (rows + PCE_ROWS - 1) / PCE_ROWS; }
+extern "C" size_t saicv_pixel_softmax_ce_ws_floats(size_t rows) { return (rows + PCE_ROWS - 1) / PCE_ROWS; }
 
 static int pce_check(const char* what, const void* logits, size_t rows, int C) {
     SAICV_REQUIRE(logits != nullptr, "%s: null logits", what);
@@ -245,10 +246,11 @@ static int pce_check(const char* what, const void* logits, size_t rows, int C) {
     return 0;
 }
 
-int pixel_softmax_ce_fwd(int dtype, const void* logits, const float* label, size_t rows, int C, float* lse, float* partial,
-                         float* loss, hipStream_t st) {
+extern "C" int saicv_pixel_softmax_ce_fwd(int dtype, const void* logits, const float* label, size_t rows, int C, float* lse, float* partial,
+                                          float* loss, void* stream) {
+    hipStream_t st = S(stream);
     if (pce_check("pixel_softmax_ce_fwd", logits, rows, C)) return -1;
-    const int blocks = (int)pixel_softmax_ce_ws_floats(rows);
+    const int blocks = (int)saicv_pixel_softmax_ce_ws_floats(rows);
     if (dtype == SAICV_DTYPE_BF16) {
         const size_t smem = span_bytes(PCE_ROWS, C, sizeof(bf16_t));
         hipLaunchKernelGGL(pixel_ce_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), smem, st, (const bf16_t*)logits, label, (int)rows, C,
@@ -262,11 +264,12 @@ int pixel_softmax_ce_fwd(int dtype, const void* logits, const float* label, size
     return check_launch("pixel_softmax_ce_fwd");
 }
 
-int pixel_softmax_ce_bwd(int dtype, const void* logits, const float* label, const float* lse, const float* upstream, size_t rows,
-                         int C, void* dlogits, hipStream_t st) {
+extern "C" int saicv_pixel_softmax_ce_bwd(int dtype, const void* logits, const float* label, const float* lse, const float* upstream, size_t rows,
+                                          int C, void* dlogits, void* stream) {
+    hipStream_t st = S(stream);
     if (pce_check("pixel_softmax_ce_bwd", logits, rows, C)) return -1;
     SAICV_REQUIRE(((uintptr_t)dlogits & 15) == 0 && dlogits != nullptr, "pixel_softmax_ce_bwd: the gradient must start on a 16-byte boundary");
-    const int blocks = (int)pixel_softmax_ce_ws_floats(rows);
+    const int blocks = (int)saicv_pixel_softmax_ce_ws_floats(rows);
     if (dtype == SAICV_DTYPE_BF16)
         hipLaunchKernelGGL(pixel_ce_bwd_kernel<bf16_t>, dim3(blocks), dim3(256), span_bytes(PCE_ROWS, C, sizeof(bf16_t)), st,
                            (const bf16_t*)logits, label, lse, upstream, (int)rows, C, (bf16_t*)dlogits);
@@ -276,8 +279,10 @@ int pixel_softmax_ce_bwd(int dtype, const void* logits, const float* label, cons
     return check_launch("pixel_softmax_ce_bwd");
 }
 
-int cpfe_gather_fwd(int dtype, const float* z, long ldz, void* out, int N, int H, int W, int P, int nb, const int* dil,
-                    hipStream_t st) {
+extern "C" int saicv_cpfe_gather_fwd(int dtype, const float* z, long ldz, void* out, int N, int H, int W, int P, int nb, int d0, int d1,
+                                     int d2, void* stream) {
+    const int dil[3] = {d0, d1, d2};
+    hipStream_t st = S(stream);
     CpfeGeom g;
     if (cpfe_geom(g, N, H, W, P, nb, dil, ldz, "cpfe_gather_fwd")) return -1;
     SAICV_REQUIRE(ldz >= (long)(1 + 9 * nb) * P && ldz % 4 == 0 && ((uintptr_t)z & 15) == 0,
@@ -290,7 +295,10 @@ int cpfe_gather_fwd(int dtype, const float* z, long ldz, void* out, int N, int H
     return check_launch("cpfe_gather_fwd");
 }
 
-int cpfe_gather_bwd(int dtype, const void* dout, void* dz, int N, int H, int W, int P, int nb, const int* dil, hipStream_t st) {
+extern "C" int saicv_cpfe_gather_bwd(int dtype, const void* dout, void* dz, int N, int H, int W, int P, int nb, int d0, int d1, int d2,
+                                     void* stream) {
+    const int dil[3] = {d0, d1, d2};
+    hipStream_t st = S(stream);
     CpfeGeom g;
     if (cpfe_geom(g, N, H, W, P, nb, dil, 0, "cpfe_gather_bwd")) return -1;
     const size_t total = (size_t)N * H * W * ((1 + 9 * nb) * P / 4);

@@ -252,7 +252,7 @@ bool stem_bwd_stream_supported(int dtype, int N, int H, int W, int CO, int cq, i
 // routed: bit 0.  The stream kernel is built and tested but stays unrouted by default (SAICV_STEM_BWD_STREAM=2 takes it): one
 // wavefront per SIMD forms dy AND multiplies, and forming a pixel chunk costs ~300 vector instructions -- 566 us per launch against
 // the 370 us of the two kernels it replaces (profiles/stem_bwd_stream.md).
-int stem_bwd_stream_ok(int dtype, int N, int H, int W, int CO, int cq, int taps_r, int taps_s, int pk, int ps, int pp) {
+extern "C" int saicv_stem_bwd_stream_ok(int dtype, int N, int H, int W, int CO, int cq, int taps_r, int taps_s, int pk, int ps, int pp) {
     const char* es = getenv("SAICV_STEM_BWD_STREAM");
     const char* er = getenv("SAICV_STEM_BWD_MIN_ROWS");
     const int mode = es ? atoi(es) : 1;
@@ -264,7 +264,7 @@ int stem_bwd_stream_ok(int dtype, int N, int H, int W, int CO, int cq, int taps_
 }
 
 // Workspace floats of the launch: in the fast mode the weight-gradient parts (parked and folded in BOTH modes, as c3_bwd_stream's are)
-size_t stem_bwd_stream_ws_floats(int N, int H, int W) {
+extern "C" size_t saicv_stem_bwd_stream_ws_floats(int N, int H, int W) {
     int splits = 0, mps = 0;
     if (!g_deterministic && N >= 1 && H >= 1 && W >= 1 && stem_fits(N, H, W) && stem_plan(N, H, W, &splits, &mps) == 0 && splits > 1)
         return (size_t)splits * kCO * kKd;

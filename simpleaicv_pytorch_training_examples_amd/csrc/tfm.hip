@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 
 // cache policy of the LayerNorm kernels' loads: the default one (streaming loads measured neutral)
 #define LN_LD ld_chunk
@@ -1119,8 +1120,9 @@ static int layernorm_fwd_t(const void* x, const float* gamma, const float* beta,
     return check_launch("layernorm_fwd");
 }
 
-int layernorm_fwd(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* mean,
-                  float* rstd, int M, int C, double eps, hipStream_t st) {
+extern "C" int saicv_layernorm_fwd(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* mean,
+                                   float* rstd, int M, int C, double eps, void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0 && M > 0, "layernorm_fwd: C=%d must be a multiple of %d", C, n);
     if (dtype == SAICV_DTYPE_BF16) return layernorm_fwd_t<bf16_t>(x, gamma, beta, y, mean, rstd, M, C, eps, st);
@@ -1136,9 +1138,10 @@ static LnDrop ln_drop(const void* branch, void* sum_out, double p, unsigned seed
 }
 
 // out = LayerNorm(sum), sum = x + dropout_p(branch)   (DETR's post-norm residual, reference detection/models/detr.py:89,92,114,118,122)
-int dropout_add_layernorm_fwd(int dtype, const void* x, const void* branch, double p, unsigned seed, const unsigned* seed_device,
-                              const float* gamma, const float* beta, void* sum_out, void* y, float* mean, float* rstd, int M, int C,
-                              double eps, hipStream_t st) {
+extern "C" int saicv_dropout_add_layernorm_fwd(int dtype, const void* x, const void* branch, double p, unsigned seed, const unsigned* seed_device,
+                                               const float* gamma, const float* beta, void* sum_out, void* y, float* mean, float* rstd, int M, int C,
+                                               double eps, void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0 && M > 0 && branch && sum_out && p >= 0.0 && p < 1.0, "dropout_add_layernorm_fwd: C=%d (multiple of %d), p=%g in [0, 1)", C, n, p);
     const LnDrop dr = ln_drop(branch, sum_out, p, seed, seed_device);
@@ -1156,7 +1159,7 @@ static int ln_bwd_blocks(int M, int* rows_per) {
     return (M + LNB_WAVES * rp - 1) / (LNB_WAVES * rp);
 }
 
-size_t layernorm_bwd_ws_floats(int M, int C) {
+extern "C" size_t saicv_layernorm_bwd_ws_floats(int M, int C) {
     int rp;
     return (size_t)2 * ln_bwd_blocks(M, &rp) * C;
 }
@@ -1190,9 +1193,10 @@ static int layernorm_bwd_t(const void* dy, const void* x, const float* gamma, co
 }
 
 // The backward of dropout_add_layernorm_fwd: dsum (= the gradient of x) and dbranch = mask / (1 - p) * dsum in one pass
-int dropout_add_layernorm_bwd(int dtype, const void* dy, const void* sum, const float* gamma, const float* mean, const float* rstd,
-                              double p, unsigned seed, const unsigned* seed_device, void* dsum, void* dbranch, float* dgamma,
-                              float* dbeta, float* ws, int M, int C, int accumulate, hipStream_t st) {
+extern "C" int saicv_dropout_add_layernorm_bwd(int dtype, const void* dy, const void* sum, const float* gamma, const float* mean, const float* rstd,
+                                               double p, unsigned seed, const unsigned* seed_device, void* dsum, void* dbranch, float* dgamma,
+                                               float* dbeta, float* ws, int M, int C, int accumulate, void* stream) {
+    hipStream_t st = S(stream);
     const int n = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(C % n == 0 && M > 0 && dbranch && p >= 0.0 && p < 1.0, "dropout_add_layernorm_bwd: C=%d (multiple of %d), p=%g in [0, 1)", C, n, p);
     const LnDrop dr = ln_drop(sum, nullptr, p, seed, seed_device);        // (branch != nullptr marks the dropout form of the second output)
@@ -1214,7 +1218,8 @@ int layernorm_bwd(int dtype, const void* dy, const void* x, const float* gamma, 
     return layernorm_bwd_t<float>(dy, x, gamma, mean, rstd, addend, dx, dgamma, dbeta, ws, M, C, accumulate, st, out_scale, rows_per_scale, dxs);
 }
 
-int gelu_fwd(int dtype, const void* x, void* y, size_t n, hipStream_t st) {
+extern "C" int saicv_gelu_fwd(int dtype, const void* x, void* y, size_t n, void* stream) {
+    hipStream_t st = S(stream);
     const int e = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(n % e == 0, "gelu_fwd: length must be a multiple of %d", e);
     if (dtype == SAICV_DTYPE_BF16)
@@ -1224,7 +1229,8 @@ int gelu_fwd(int dtype, const void* x, void* y, size_t n, hipStream_t st) {
     return check_launch("gelu_fwd");
 }
 
-int gelu_bwd(int dtype, const void* dy, const void* x, void* dx, size_t n, hipStream_t st) {
+extern "C" int saicv_gelu_bwd(int dtype, const void* dy, const void* x, void* dx, size_t n, void* stream) {
+    hipStream_t st = S(stream);
     const int e = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
     SAICV_REQUIRE(n % e == 0, "gelu_bwd: length must be a multiple of %d", e);
     if (dtype == SAICV_DTYPE_BF16)
@@ -1242,7 +1248,8 @@ static int relu_dropout_check(const char* who, int dtype, size_t n, double p) {
     return 0;
 }
 
-int relu_dropout_fwd(int dtype, const void* x, void* y, size_t n, double p, unsigned seed, const unsigned* seed_device, hipStream_t st) {
+extern "C" int saicv_relu_dropout_fwd(int dtype, const void* x, void* y, size_t n, double p, unsigned seed, const unsigned* seed_device, void* stream) {
+    hipStream_t st = S(stream);
     if (relu_dropout_check("relu_dropout_fwd", dtype, n, p)) return -1;
     if (n == 0) return 0;
     const int e = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
@@ -1255,7 +1262,8 @@ int relu_dropout_fwd(int dtype, const void* x, void* y, size_t n, double p, unsi
     return check_launch("relu_dropout_fwd");
 }
 
-int relu_dropout_bwd(int dtype, const void* dy, const void* y, void* dx, size_t n, double p, hipStream_t st) {
+extern "C" int saicv_relu_dropout_bwd(int dtype, const void* dy, const void* y, void* dx, size_t n, double p, void* stream) {
+    hipStream_t st = S(stream);
     if (relu_dropout_check("relu_dropout_bwd", dtype, n, p)) return -1;
     if (n == 0) return 0;
     const int e = dtype == SAICV_DTYPE_BF16 ? 8 : 4;
@@ -1274,8 +1282,9 @@ static int attn_check(const char* who, int B, int N, int H, int D) {
     return 0;
 }
 
-int attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int N, int H, int D, double scale,
-                  hipStream_t st) {
+extern "C" int saicv_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int N, int H, int D, double scale,
+                                   void* stream) {
+    hipStream_t st = S(stream);
     if (attn_check("attention_fwd", B, N, H, D)) return -1;
     const int Np = (N + 31) & ~31;
     if (dtype == SAICV_DTYPE_BF16) {
@@ -1294,8 +1303,9 @@ int attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int 
     return check_launch("attention_fwd");
 }
 
-int attention_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
-                  int B, int N, int H, int D, double scale, hipStream_t st) {
+extern "C" int saicv_attention_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
+                                   int B, int N, int H, int D, double scale, void* stream) {
+    hipStream_t st = S(stream);
     if (attn_check("attention_bwd", B, N, H, D)) return -1;
     const int Np = (N + 31) & ~31;
     // bf16: SAICV_ATTN_BWD2=1 selects the two-tiles-per-wavefront kernel.  Measured equal on the ViT-B step (42.58 vs 42.64 ms,

@@ -14,6 +14,7 @@
 //     exact zeros in the same launch.
 #include "common.h"
 #include "saicv_internal.h"
+#include "../../include/saicv_hip.h"
 #include "ordered_sum.h"
 
 namespace {
@@ -263,12 +264,13 @@ int chunks_of(size_t P) { return (int)((P + US_CHUNK - 1) / US_CHUNK); }
 
 namespace saicv {
 
-int univseg_chunk() { return US_CHUNK; }
+extern "C" int saicv_univseg_chunk() { return US_CHUNK; }
 
-size_t univseg_pair_ws_floats(int B, int Q, int TT, size_t P) { return (size_t)chunks_of(P) * pair_ld(B, Q, TT); }
+extern "C" size_t saicv_univseg_pair_ws_floats(int B, int Q, int TT, size_t P) { return (size_t)chunks_of(P) * pair_ld(B, Q, TT); }
 
-int univseg_pair_sums(int dtype, const void* preds, const float* targets, const int* offsets, int B, int Q, int TT, int Tmax, size_t P,
-                      float* partial, float* sums, hipStream_t st) {
+extern "C" int saicv_univseg_pair_sums(int dtype, const void* preds, const float* targets, const int* offsets, int B, int Q, int TT, int Tmax, size_t P,
+                                       float* partial, float* sums, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(B > 0 && Q > 0 && P > 0 && TT >= 0 && Tmax >= 0 && Tmax <= TT, "univseg_pair_sums: B=%d Q=%d P=%zu T=%d Tmax=%d", B,
                   Q, P, TT, Tmax);
     SAICV_REQUIRE(dtype == SAICV_DTYPE_BF16 || dtype == SAICV_DTYPE_F32, "univseg_pair_sums: dtype %d", dtype);
@@ -290,10 +292,11 @@ int univseg_pair_sums(int dtype, const void* preds, const float* targets, const 
     return check_launch("univseg_pair_fold");
 }
 
-size_t univseg_matched_ws_floats(int M, size_t P) { return (size_t)M * chunks_of(P) * 4; }
+extern "C" size_t saicv_univseg_matched_ws_floats(int M, size_t P) { return (size_t)M * chunks_of(P) * 4; }
 
-int univseg_matched_fwd(int dtype, const void* preds, const float* targets, const int* rowx, const int* rowy, int M, size_t P,
-                        float* partial, float* stats, hipStream_t st) {
+extern "C" int saicv_univseg_matched_fwd(int dtype, const void* preds, const float* targets, const int* rowx, const int* rowy, int M, size_t P,
+                                         float* partial, float* stats, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(M >= 0 && P > 0 && M <= 65535, "univseg_matched_fwd: M=%d P=%zu", M, P);
     SAICV_REQUIRE(dtype == SAICV_DTYPE_BF16 || dtype == SAICV_DTYPE_F32, "univseg_matched_fwd: dtype %d", dtype);
     if (M == 0) return 0;
@@ -311,8 +314,9 @@ int univseg_matched_fwd(int dtype, const void* preds, const float* targets, cons
     return check_launch("univseg_matched_fold");
 }
 
-int univseg_matched_bwd(int dtype, const void* preds, const float* targets, const int* rowmap, const int* rowy, const float* gstats,
-                        int R, size_t P, void* dpreds, hipStream_t st) {
+extern "C" int saicv_univseg_matched_bwd(int dtype, const void* preds, const float* targets, const int* rowmap, const int* rowy, const float* gstats,
+                                         int R, size_t P, void* dpreds, void* stream) {
+    hipStream_t st = S(stream);
     SAICV_REQUIRE(R > 0 && P > 0 && R <= 65535, "univseg_matched_bwd: rows=%d P=%zu", R, P);
     SAICV_REQUIRE(dtype == SAICV_DTYPE_BF16 || dtype == SAICV_DTYPE_F32, "univseg_matched_bwd: dtype %d", dtype);
     const bool vec = P % 8 == 0 && aligned16(preds) && aligned16(targets) && aligned16(dpreds);
