@@ -172,7 +172,8 @@ __global__ void scaler_update_kernel(float* __restrict__ state, const float* __r
     } else {
         const float t = state[1] + 1.f;
         if ((int)t >= interval) {
-            state[0] *= growth;
+            const float grown = state[0] * growth;
+            if (fabsf(grown) <= 3.4028234e38f) state[0] = grown;     // torch's _amp_update_scale_ never grows the scale into inf
             state[1] = 0.f;
         } else {
             state[1] = t;
