@@ -683,6 +683,34 @@ int saicv_univseg_matched_fwd(int dtype, const void* mask_preds, const float* ta
 int saicv_univseg_matched_bwd(int dtype, const void* mask_preds, const float* targets, const int* row_pair, const int* target_rows,
                               const float* gstats, int rows, size_t P, void* dmask_preds, void* stream);
 
+/* ---- universal matting (universal_segmentation/matting_losses.py: Mask2FormerHungarianMatcher; models/dinov3_universal_matting.py:
+ * predict's sigmoids and collaborative_matting; csrc/unimat.hip).
+ * Pair sums: fp32 probabilities read IN PLACE through element strides -- global (b, q, c, i) at b * gsb + q * gsq + c * gsc + i * gsp,
+ * local and fused (b, q, i) likewise; [B][Q][3][P] contiguous (3QP, 3P, P, 1) and channels-last [B][P][3Q] memory (3QP, 3, 1, 3Q)
+ * both take 16-byte loads.  trimaps, alphas [total_t][P] fp32 packed image after image, offsets [B + 1] int32 in device memory, max_t
+ * the largest count (an image may own no target).  With every probability clamped to [1e-4, 1 - 1e-4], k the trimap class (255 -> 2,
+ * else anything > 2 -> 1, else the integer part) and w = [trimap == 128], sums (5 * Q * total_t + B * Q + total_t floats) = five
+ * planes [Q][total_t] -- sum -log g_k, sum over the two other channels of -log(1 - g_c), sum g_k, sum w |l - a|, sum |f - a|, column
+ * offsets[i] + t paired with the queries of image i only -- then sum_p sum_c g [B][Q], then sum w [total_t].  Terms are selected,
+ * never subtracted; the logarithms of a (query, pixel) are taken once per group of up to 8 targets; pixel chunks of
+ * saicv_unimat_chunk() are added in chunk order: no atomics, the bits of an image's sums depend on (Q, T_i, P) alone.
+ * partial: saicv_unimat_pair_ws_floats floats. */
+int saicv_unimat_chunk(void);
+size_t saicv_unimat_pair_ws_floats(int B, int Q, int total_t, size_t P);
+int saicv_unimat_pair_sums(const float* global_preds, long gsb, long gsq, long gsc, long gsp, const float* local_preds, long lsb,
+                           long lsq, long lsp, const float* fused_preds, long fsb, long fsq, long fsp, const float* trimaps,
+                           const float* alphas, const int* offsets, int B, int Q, int total_t, int max_t, size_t P, float* partial,
+                           float* sums, void* stream);
+/* The head on channels-last memory: global_logits [rows][3 Q] (channel 3 q + c) and local_logits [rows][Q] in dtype (bf16 or fp32),
+ * rows = B * H * W -> fp32 global_preds = sigmoid, local_preds = sigmoid, fused_preds = local [argmax == 1] + [argmax == 2] with the
+ * argmax over the three fp32 probabilities, the first maximum on ties (torch.max).  One read and one write per element. */
+int saicv_unimat_head_fwd(int dtype, const void* global_logits, const void* local_logits, size_t rows, int Q, float* global_preds,
+                          float* local_preds, float* fused_preds, void* stream);
+/* dglobal_logits = dG g (1 - g), dlocal_logits = (dL + dF [argmax == 1]) l (1 - l), in dtype, from the saved probabilities */
+int saicv_unimat_head_bwd(int dtype, const float* global_preds, const float* local_preds, const float* dglobal_preds,
+                          const float* dlocal_preds, const float* dfused_preds, size_t rows, int Q, void* dglobal_logits,
+                          void* dlocal_logits, void* stream);
+
 /* One bidirectional LSTM layer's recurrence (nn.LSTM: one layer, batch_first, zero initial state, gate order i, f, g, o; csrc/lstm.hip).
  * The input projection and every parameter / input gradient are GEMMs on the entry points above; these two walk T.  H a multiple of
  * 32 in 32 .. 1024, any B >= 1 and T >= 1; both directions in one launch, no atomics, nothing read back.

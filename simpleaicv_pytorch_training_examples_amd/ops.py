@@ -2996,3 +2996,163 @@ def matched_mask_stats(mask_preds, targets, pair_b, pair_q, pair_t):
     dev = mask_preds.device
     return MatchedMaskStatsFn.apply(mask_preds, targets, rows.to(torch.int32).to(dev, non_blocking=True),
                                     pt.to(torch.int32).to(dev, non_blocking=True), rowmap.to(dev, non_blocking=True))
+
+
+# ------------------------------------------------------------------------------ universal matting (csrc/unimat.hip)
+MATTING_PAIR_SUMS = ('ce_pos', 'ce_neg', 'intersection', 'local_l1', 'fused_l1')
+
+
+def matting_pair_chunk():
+    """Pixels per workgroup of the matting pair-sum kernel: H * W is split into chunks of this length, added in chunk order."""
+    return int(lib().saicv_unimat_chunk())
+
+
+def _matting_pred(t, channels, name):
+    """[B, Q, channels, H, W] probabilities -> (fp32 tensor, (sb, sq, sc, sp)), read in place whenever the pixels of a (b, q, c) map
+    lie one stride apart (the contiguous and the channels-last order both do); anything else through a contiguous copy"""
+    if t.dim() != 5 or t.shape[2] != channels:
+        raise ValueError(f'{name} must be [B, Q, {channels}, H, W], got {tuple(t.shape)}')
+    if t.dtype != torch.float32:
+        t = t.float()
+    h, w = t.shape[3], t.shape[4]
+    if (h > 1 and w > 1 and t.stride(3) != w * t.stride(4)) or any(s < 0 for s in t.stride()):
+        t = t.contiguous()
+    sp = t.stride(4) if w > 1 else (t.stride(3) if h > 1 else 1)
+    return t, (t.stride(0), t.stride(1), t.stride(2), sp)
+
+
+def matting_pair_sums(global_preds, local_preds, fused_preds, trimaps, alphas, offsets):
+    """global_preds [B, Q, 3, H, W], local_preds and fused_preds [B, Q, 1, H, W] fp32 probabilities in any memory order whose
+    pixel axis is one stride (read in place); trimaps, alphas [sum T_i, H, W] packed image after image; offsets the B + 1 row
+    bounds (T_i = 0 is legal).  -> (planes [5, Q, sum T_i] in the order MATTING_PAIR_SUMS, global_sum [B, Q], weight_sum [sum T_i]),
+    fp32; column offsets[i] + t of a plane is paired with the queries of image i.  Probabilities are clamped to [1e-4, 1 - 1e-4];
+    class k of a trimap value as in trimap_stats; ordered sums, bit-reproducible."""
+    require_gpu(global_preds, local_preds, fused_preds, trimaps, alphas)
+    b, q = global_preds.shape[0], global_preds.shape[1]
+    host = _mask_offsets(offsets, b)
+    total = host[-1]
+    gp, gs = _matting_pred(global_preds, 3, 'global_preds')
+    lp, ls = _matting_pred(local_preds, 1, 'local_preds')
+    fp, fs = _matting_pred(fused_preds, 1, 'fused_preds')
+    h, w = gp.shape[3], gp.shape[4]
+    if tuple(lp.shape) != (b, q, 1, h, w) or tuple(fp.shape) != (b, q, 1, h, w):
+        raise ValueError(f'local_preds / fused_preds must be [{b}, {q}, 1, {h}, {w}]')
+    trimaps, alphas = _f32c(trimaps), _f32c(alphas)
+    if tuple(trimaps.shape) != (total, h, w) or tuple(alphas.shape) != (total, h, w):
+        raise ValueError(f'trimaps and alphas must be the packed [{total}, {h}, {w}] maps of the batch')
+    p = h * w
+    L, dev = lib(), gp.device
+    off = torch.tensor(host, dtype=torch.int32).to(dev, non_blocking=True)
+    sums = torch.empty(5 * q * total + b * q + total, dtype=torch.float32, device=dev)
+    partial = torch.empty(L.saicv_unimat_pair_ws_floats(b, q, total, p), dtype=torch.float32, device=dev)
+    tmax = max(host[i + 1] - host[i] for i in range(b))
+    t0 = KernelTimer.begin('unimat_pair_sums')
+    check(L.saicv_unimat_pair_sums(ptr(gp), gs[0], gs[1], gs[2], gs[3], ptr(lp), ls[0], ls[1], ls[3], ptr(fp), fs[0], fs[1], fs[3],
+                                   ptr(trimaps), ptr(alphas), ptr(off), b, q, total, tmax, p, ptr(partial), ptr(sums), stream()),
+          'unimat_pair_sums')
+    KernelTimer.end(t0, 'unimat_pair_sums', 0, 20 * b * q * p + 8 * total * p)
+    plane = q * total
+    return sums[:5 * plane].view(5, q, total), sums[5 * plane:5 * plane + b * q].view(b, q), sums[5 * plane + b * q:]
+
+
+def matting_match_cost(global_preds, local_preds, fused_preds, class_preds, trimaps, alphas, offsets, labels, ce_cost=1.0,
+                       iou_cost=1.0, local_cost=1.0, fusion_cost=1.0, class_cost=1.0):
+    """The cost matrices of the universal-matting Mask2FormerHungarianMatcher (universal_segmentation/matting_losses.py) for the
+    whole batch, PACKED: fp32 [Q, sum T_i] on the device, columns offsets[i] .. offsets[i + 1) being image i's [Q, T_i] matrix
+        ce (Cpos + Cneg) / (3 P) + iou (1 - (I + 1e-4) / (G + P - I + 1e-4)) + local L / (W + 1) + fusion F / P
+        - class softmax(class_preds)[q, label_t]
+    clamped to +-1e10 with NaN -> 0 (the sums: matting_pair_sums).  One copy to the host then serves every image's assignment."""
+    b = global_preds.shape[0]
+    host = _mask_offsets(offsets, b)
+    planes, gsum, wsum = matting_pair_sums(global_preds, local_preds, fused_preds, trimaps, alphas, host)
+    dev = planes.device
+    p = float(global_preds.shape[3] * global_preds.shape[4])
+    counts = torch.tensor([host[i + 1] - host[i] for i in range(b)], dtype=torch.int64)
+    image = torch.repeat_interleave(torch.arange(b, dtype=torch.int64), counts).to(dev, non_blocking=True)
+    labels = labels.to(device=dev, dtype=torch.int64)
+    cls = class_preds.float().softmax(dim=-1)[image, :, labels].t()                 # [Q, sum T]
+    cpos, cneg, inter, lsum, fsum = planes
+    iou = 1 - (inter + 1e-4) / (gsum[image].t() + p - inter + 1e-4)
+    cost = (ce_cost * ((cpos + cneg) / (3 * p)) + iou_cost * iou + local_cost * (lsum / (wsum[None, :] + 1))
+            + fusion_cost * (fsum / p) - class_cost * cls)
+    return torch.nan_to_num(cost.clamp(min=-1e10, max=1e10), 0)
+
+
+class MattingHeadFn(torch.autograd.Function):
+    """channels-last logits [B, H, W, 3Q] and [B, H, W, Q] (bf16 or fp32) -> fp32 probabilities of the same shapes and the fused
+    prediction, one pass each way"""
+
+    @staticmethod
+    def forward(ctx, gl, ll):
+        b, h, w, q = ll.shape
+        dev = gl.device
+        g = torch.empty((b, h, w, 3 * q), dtype=torch.float32, device=dev)
+        l = torch.empty((b, h, w, q), dtype=torch.float32, device=dev)
+        f = torch.empty((b, h, w, q), dtype=torch.float32, device=dev)
+        rows = b * h * w
+        t0 = KernelTimer.begin('unimat_head')
+        check(lib().saicv_unimat_head_fwd(dtype_code(gl.dtype), ptr(gl), ptr(ll), rows, q, ptr(g), ptr(l), ptr(f), stream()),
+              'unimat_head_fwd')
+        KernelTimer.end(t0, 'unimat_head', 0, (4 * gl.element_size() + 20) * rows * q)
+        ctx.save_for_backward(g, l)
+        ctx.dtype = gl.dtype
+        return g, l, f
+
+    @staticmethod
+    def backward(ctx, dg, dl, df):
+        g, l = ctx.saved_tensors
+        b, h, w, q = l.shape
+        dg, dl, df = (t.float().contiguous() for t in (dg, dl, df))
+        dgl = torch.empty(g.shape, dtype=ctx.dtype, device=g.device)
+        dll = torch.empty(l.shape, dtype=ctx.dtype, device=g.device)
+        t0 = KernelTimer.begin('unimat_head')
+        check(lib().saicv_unimat_head_bwd(dtype_code(ctx.dtype), ptr(g), ptr(l), ptr(dg), ptr(dl), ptr(df), b * h * w, q, ptr(dgl),
+                                          ptr(dll), stream()), 'unimat_head_bwd')
+        KernelTimer.end(t0, 'unimat_head', 0, (4 * dgl.element_size() + 36) * b * h * w * q)
+        return dgl, dll
+
+
+def matting_head(global_logits, local_logits):
+    """The end of UniversalMatting.predict: global_logits [B, 3Q, H, W] (channel 3 q + c) and local_logits [B, Q, H, W], bf16 or
+    fp32; channels-last memory is read in place, any other order through a copy.  -> (global_preds [B, Q, 3, H, W], local_preds
+    [B, Q, 1, H, W], fused_preds [B, Q, 1, H, W]), fp32 VIEWS of channels-last memory: sigmoid, sigmoid, and
+    local [argmax == 1] + [argmax == 2] with the argmax over the three fp32 probabilities (first maximum on ties, torch.max)."""
+    require_gpu(global_logits, local_logits)
+    if global_logits.dim() != 4 or local_logits.dim() != 4 or global_logits.shape[1] != 3 * local_logits.shape[1] \
+            or global_logits.shape[0] != local_logits.shape[0] or global_logits.shape[2:] != local_logits.shape[2:]:
+        raise ValueError(f'matting_head: global_logits {tuple(global_logits.shape)} must be [B, 3Q, H, W] for local_logits '
+                         f'{tuple(local_logits.shape)} = [B, Q, H, W]')
+    if global_logits.dtype != local_logits.dtype or global_logits.dtype not in (torch.float32, torch.bfloat16):
+        global_logits, local_logits = global_logits.float(), local_logits.float()
+    b, q, h, w = local_logits.shape
+    g, l, f = MattingHeadFn.apply(global_logits.permute(0, 2, 3, 1).contiguous(), local_logits.permute(0, 2, 3, 1).contiguous())
+    return (g.view(b, h, w, q, 3).permute(0, 3, 4, 1, 2), l.view(b, h, w, q, 1).permute(0, 3, 4, 1, 2),
+            f.view(b, h, w, q, 1).permute(0, 3, 4, 1, 2))
+
+
+class TakeRowsFn(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, x, pb, pq):
+        ctx.save_for_backward(pb, pq)
+        ctx.layout = (tuple(x.shape), tuple(x.stride()), x.dtype)
+        return x[pb, pq].contiguous()
+
+    @staticmethod
+    def backward(ctx, g):
+        pb, pq = ctx.saved_tensors
+        shape, stride, dtype = ctx.layout
+        dx = torch.empty_strided(shape, stride, dtype=dtype, device=g.device).zero_()
+        dx[pb, pq] = g.to(dtype)
+        return dx, None, None
+
+
+def take_rows(x, pair_b, pair_q):
+    """x [B, Q, ...] -> the M rows x[pair_b[m], pair_q[m]] as one contiguous tensor [M, ...].  The backward allocates the zero
+    gradient in x's OWN memory order (a channels-last view stays one) and writes the M rows into it, so the full-size gradient is
+    written once and reaches the producer of x without a layout copy.  x must be dense (no overlapping or broadcast strides)."""
+    pb = torch.as_tensor(pair_b, dtype=torch.int64).reshape(-1).to(x.device)
+    pq = torch.as_tensor(pair_q, dtype=torch.int64).reshape(-1).to(x.device)
+    if pb.numel() != pq.numel():
+        raise ValueError('take_rows: pair_b and pair_q must have one length')
+    return TakeRowsFn.apply(x, pb, pq)
